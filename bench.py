@@ -7,6 +7,14 @@ Default workload = BASELINE.json configs[1]: TLS 1.3 AES-256-GCM *decrypt* of
 tlsrec_batch_decrypt call over the whole batch (one kernel launch).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs);
+the inputs are seeded, so two builds can be compared output for output.
+--full adds everything else after the timed steps: the status / plaintext
+check of the timed batch, the oracle spot check, the CPU baseline legs and
+the host-buffer (e2e) leg (--no-cpu, --no-e2e and --verify trim them).
 
 Multi-GPU: `python bench.py --gpus N` starts N rank processes itself (one per
 GPU, before any GPU call in the parent; launch_ranks), or runs as one rank of
@@ -92,17 +100,25 @@ def parse():
     ap.add_argument("--keys", type=int, default=0, help="override the config's key count (records round-robin over keys)")
     ap.add_argument("--lanes", type=int, default=0)
     ap.add_argument("--align", type=int, default=128, help="record slot alignment in the arena (bytes; 128 = HBM/L2 line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks against the oracle, the CPU baseline legs and "
+                         "the host-buffer (e2e) leg; a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's shard; see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="wall-time target of the CPU sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (pinned H2D/D2H) leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-buffer (pinned H2D/D2H) leg")
     ap.add_argument("--dist", action="store_true",
                     help="use the process group even at WORLD_SIZE=1 (rehearses the RCCL path on one GPU)")
     ap.add_argument("--e2e-records", type=int, default=0, help="records of the end-to-end leg (0 = ~2 GiB worth)")
-    ap.add_argument("--verify", type=int, default=64, help="records spot-checked against the oracle")
+    ap.add_argument("--verify", type=int, default=64, help="with --full: records spot-checked against the oracle")
     ap.add_argument("--key-order", choices=["round-robin", "contiguous"], default="round-robin",
                     help="record i under key i %% keys (default, SURVEY 8(d)-4) or i // (records / keys) "
                          "(diagnostic: a key's descriptors adjacent in memory)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(*a):
@@ -329,7 +345,10 @@ def main():
     sh = M.shard_bounds(n * world, rank, world)
     assert sh.count == n
     shard0 = sh.start
-    arena = torch.randint(0, 256, (n * stride,), dtype=torch.uint8, device=dev)
+    # seeded per rank: the same arguments give the same inputs from run to run
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(SEED + rank)
+    arena = torch.randint(0, 256, (n * stride,), dtype=torch.uint8, device=dev, generator=gen)
     recs = M.records(n)
     recs["buf_off"] = np.arange(n, dtype=np.uint64) * stride + lead
     recs["buf_len"] = stride - lead
@@ -347,7 +366,8 @@ def main():
     recs["ver"] = (3, 3)
     recs_dev = torch.from_numpy(recs.view(np.uint8).copy()).to(dev)
     res_dev = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
-    sample = list(range(0, n, max(1, n // max(1, args.verify))))[:args.verify]
+    verify = args.verify if args.full else 0
+    sample = list(range(0, n, max(1, n // max(1, verify))))[:verify]
     pt_sample = {i: arena[i * stride + lead + head:i * stride + lead + head + content].cpu().numpy().copy()
                  for i in sample}
 
@@ -395,24 +415,31 @@ def main():
     kern_ms = [a.elapsed_time(b) for a, b in evs]
     wall, kern_ranks = rank_timing(dist if distributed else None, wall, kern_ms, dev)
 
-    # ---- correctness of what was timed ----------------------------------------
-    st = res_dev.view(torch.int32)[0::4]
-    bad = int((st != 0).sum())
-    lens = res_dev.view(torch.int32)[2::4]
-    if direction == "decrypt":
-        bad += int((lens != content).sum())
-        for i in sample:
-            got = out_arena[i * stride + lead + head:i * stride + lead + head + content].cpu().numpy()
-            bad += int(not np.array_equal(got, pt_sample[i]))
-    bad_t = torch.tensor([bad], dtype=torch.int64, device=dev)
-    if distributed:
-        dist.all_reduce(bad_t)
-    bad = int(bad_t.item())
+    # ---- what the last timed step computed, for output-by-output comparison ----
+    if args.dump_outputs and rank == 0:
+        lo, hi = (lead + head, lead + head + content) if direction == "decrypt" else (lead, lead + wire)
+        dump_outputs(args.dump_outputs, out_arena, res_dev, n, stride, lo, hi)
+
+    # ---- correctness of what was timed (--full) ---------------------------------
+    bad = None
+    if args.full:
+        st = res_dev.view(torch.int32)[0::4]
+        bad = int((st != 0).sum())
+        lens = res_dev.view(torch.int32)[2::4]
+        if direction == "decrypt":
+            bad += int((lens != content).sum())
+            for i in sample:
+                got = out_arena[i * stride + lead + head:i * stride + lead + head + content].cpu().numpy()
+                bad += int(not np.array_equal(got, pt_sample[i]))
+        bad_t = torch.tensor([bad], dtype=torch.int64, device=dev)
+        if distributed:
+            dist.all_reduce(bad_t)
+        bad = int(bad_t.item())
 
     # oracle spot check of the bytes (rank 0, sample): the ciphertext the
     # GPU produced must equal the CPU restatement's for the same inputs
     oracle_ok = None
-    if rank == 0 and args.verify:
+    if rank == 0 and verify:
         import oracle as O
         oc = {c: c for c in M.KEYLEN}      # the oracle shares the cipher ids
         oracle_ok = True
@@ -486,7 +513,7 @@ def main():
     payload_total = float(n) * inner * world
     value = payload_total / steps_s / 2**30
 
-    # the CPU leg and the host-buffer leg run on rank 0 at every world size,
+    # --full: the CPU leg and the host-buffer leg run on rank 0 at every world size,
     # after the timed region (the other ranks wait at a barrier): records in
     # host memory are pinned socket buffers -> device -> pinned (the boundary
     # the reference's callers hand over, ssl_msg.c:1855 / :2058), reported
@@ -496,7 +523,7 @@ def main():
     run_e2e = None if args.no_e2e else (
         lambda: end_to_end(M, kt, recs, arena, out_arena, n, stride, lead, head, content, wire, inner, direction,
                            args.e2e_records))
-    cpu, e2e = rank0_legs(dist if distributed else None, rank, run_cpu, run_e2e)
+    cpu, e2e = rank0_legs(dist if distributed else None, rank, run_cpu, run_e2e) if args.full else (None, None)
 
     if world > 1 and args.config == "c2":
         # BASELINE configs[4] (c5): the c2 shard on every rank, keys broadcast over RCCL
@@ -537,13 +564,55 @@ def main():
                      "kernel_ms_max_over_ranks": per_rank["kernel_ms_max"]},
         "cpu_baseline": cpu,
         "e2e": e2e,
-        "check": {"bad_records": bad, "oracle_sample_ok": oracle_ok},
+        "check": {"bad_records": bad, "oracle_sample_ok": oracle_ok} if args.full else None,
+        "full": args.full,
+        "dump_outputs": args.dump_outputs,
         "dist": dist_info,
     }
     if rank == 0:
         print(json.dumps(out), flush=True)
     if distributed:
         dist.destroy_process_group()
+
+
+DUMP_PER_RECORD = 1 << 21      # records whose result and byte sum are written (4 + 1 float32 each)
+DUMP_BYTES = 2 << 20           # output bytes written verbatim (one float32 each)
+
+
+def dump_outputs(path, out_arena, res_dev, n, stride, lo, hi):
+    """What a caller of the timed batch call receives from its last step, as
+    float32 .npy files under `path` (under 64 MB in all):
+
+    results.npy           (k, 4): status, data_offset, data_len, type of k records
+    record_byte_sums.npy  (k,):   the sum of the output bytes [lo, hi) of each of those records' slots
+    record_bytes.npy      (s, hi - lo): the output bytes of s of them, verbatim
+
+    k = every record up to DUMP_PER_RECORD, else a sorted sample of that many;
+    s = as many of them, evenly spaced, as DUMP_BYTES holds.  Both samples are
+    drawn from SEED alone, so two runs with the same arguments write the same
+    records.  Every value is an integer below 2^24 in magnitude, exact in
+    float32.  Bytes of a slot outside [lo, hi) are not output and not read."""
+    import torch
+    assert (hi - lo) * 255 < 1 << 24
+    os.makedirs(path, exist_ok=True)
+    if n <= DUMP_PER_RECORD:
+        per = np.arange(n, dtype=np.int64)
+    else:
+        rng = np.random.RandomState(SEED & 0xFFFFFFFF)
+        per = np.sort(rng.choice(n, DUMP_PER_RECORD, replace=False)).astype(np.int64)
+    idx = torch.from_numpy(per).to(out_arena.device)
+    res = res_dev.view(n, 16)[idx]
+    words = res.view(torch.int32).view(-1, 4)
+    results = torch.stack([words[:, 0], words[:, 1], words[:, 2], res[:, 12].to(torch.int32)], dim=1)
+    np.save(os.path.join(path, "results.npy"), results.cpu().numpy().astype(np.float32))
+    rows = out_arena.view(n, stride)
+    sums = torch.empty(len(per), dtype=torch.int64, device=out_arena.device)
+    for c in range(0, len(per), 16384):
+        sums[c:c + 16384] = rows[idx[c:c + 16384]][:, lo:hi].sum(dim=1, dtype=torch.int64)
+    np.save(os.path.join(path, "record_byte_sums.npy"), sums.cpu().numpy().astype(np.float32))
+    s = max(1, min(len(per), DUMP_BYTES // max(1, hi - lo)))
+    pick = idx[torch.from_numpy(np.arange(s, dtype=np.int64) * len(per) // s).to(idx.device)]
+    np.save(os.path.join(path, "record_bytes.npy"), rows[pick][:, lo:hi].cpu().numpy().astype(np.float32))
 
 
 def rank_evidence(dist, keys_dev, dev, local):

@@ -18,7 +18,7 @@ for row in "$@"; do
     stream_cp) cmd=(python3 tools/bench_stream.py --conns 262144 --recs 4 --content 1400 --cipher 3) ;;
     dtls_cp) cmd=(python3 tools/bench_dtls.py --cipher 3) ;;
     dtls16k) cmd=(python3 tools/bench_dtls.py --content 16384 --recs 4 --cipher 2) ;;
-    *) cmd=(python3 bench.py --config $row --no-cpu --no-e2e --verify 16) ;;
+    *) cmd=(python3 bench.py --full --config $row --no-cpu --no-e2e --verify 16) ;;
   esac
   k=0
   for v in "$A" "$B" "$B" "$A"; do

@@ -15,8 +15,8 @@ row() {   # name, timeout, command...
 summ() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d.get('roofline') or {}; print(sys.argv[2], d.get('value'), r.get('kernel_ms_avg'), r.get('frac'), r.get('traffic'), (d.get('cpu_baseline') or {}).get('value'), d.get('check'))" $O/$1.json $1; }
 case "$1" in
 base)
-  row c2 300 python3 bench.py --no-cpu --no-e2e && summ c2 &&
-  for c in c4s c2s; do row $c 300 python3 bench.py --config $c --no-cpu --no-e2e && summ $c || exit 1; done &&
+  row c2 300 python3 bench.py --full --no-cpu --no-e2e && summ c2 &&
+  for c in c4s c2s; do row $c 300 python3 bench.py --full --config $c --no-cpu --no-e2e && summ $c || exit 1; done &&
   row stream16s 300 python3 tools/bench_stream.py --conns 65536 --recs 16 --content 1400 && cat $O/stream16s.json &&
   row dtls_small 300 python3 tools/bench_dtls.py && cat $O/dtls_small.json
   ;;
@@ -67,7 +67,7 @@ libab)   # same-box A/B of two libraries on bench.py configs: LIBA LIBB CONFIGS 
   : > $O/libab.txt
   for c in $CONFIGS; do for lib in $LIBA $LIBB $LIBB $LIBA; do
     tag=$(basename $lib .so)
-    TLSREC_LIBRARY=$R/$lib timeout -k 10 300 python3 bench.py --config $c --no-cpu --no-e2e --verify 16 > $O/t.json 2> $O/t.err || { echo "FAIL $c $tag"; tail -3 $O/t.err; exit 1; }
+    TLSREC_LIBRARY=$R/$lib timeout -k 10 300 python3 bench.py --full --config $c --no-cpu --no-e2e --verify 16 > $O/t.json 2> $O/t.err || { echo "FAIL $c $tag"; tail -3 $O/t.err; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], sys.argv[3], d['value'], d['roofline']['kernel_ms_avg'], d['check']['bad_records'])" $O/t.json $c $tag | tee -a $O/libab.txt
   done; done
   ;;
@@ -77,7 +77,7 @@ multiab)   # same-box A/B of several libraries (LIBS) on bench configs (CONFIGS)
     lib=${ent%%:*}; envs=""; [ "$ent" != "$lib" ] && envs=$(echo "${ent#*:}" | tr ',' ' ')
     tag=$(basename $lib .so)${envs:+:$envs}
     for c in $CONFIGS; do
-      env $envs TLSREC_LIBRARY=$R/$lib timeout -k 10 300 python3 bench.py --config $c --no-cpu --no-e2e --verify 16 > $O/t.json 2> $O/t.err || { echo "FAIL $c $tag"; tail -3 $O/t.err; exit 1; }
+      env $envs TLSREC_LIBRARY=$R/$lib timeout -k 10 300 python3 bench.py --full --config $c --no-cpu --no-e2e --verify 16 > $O/t.json 2> $O/t.err || { echo "FAIL $c $tag"; tail -3 $O/t.err; exit 1; }
       python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(json.dumps(dict(row=sys.argv[2], lib=sys.argv[3], rep=$rep, value=d['value'], kernel_ms=d['roofline']['kernel_ms_avg'], bad=d['check']['bad_records'])))" $O/t.json $c $tag >> $O/multiab.jsonl
     done
     for name in $ROWS; do
@@ -149,15 +149,15 @@ rows)   # the round's one full sweep on the final build: -m gpu suite, smoke, ev
   tail -1 $O/gpu_tests.txt
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { echo "smoke failed"; tail -5 $O/smoke.txt; exit 1; }
   tail -1 $O/smoke.txt
-  row c2 400 python3 bench.py && summ c2 &&
+  row c2 400 python3 bench.py --full && summ c2 &&
   for c in c3 c4 c4s k4 c1 c2s c3d chacha16k gcm192 ccm ccm8 aria256 camellia128; do
-    row $c 400 python3 bench.py --config $c --no-e2e && summ $c || exit 1
+    row $c 400 python3 bench.py --full --config $c --no-e2e && summ $c || exit 1
   done
   [ "${ROWS_SPLIT:-0}" = 1 ] && { echo "rows part 1 done"; exit 0; }
   ;&
 rows2)   # the second half of rows (ROWS_SPLIT=1 rows, then rows2: each call under gpurun's 20-minute limit)
   row count_gpus 60 python3 -c "import bench, json; print(json.dumps({'count_gpus': bench.count_gpus()}))" && cat $O/count_gpus.json &&
-  row dist1 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --dist && summ dist1 &&
+  row dist1 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --dist --full && summ dist1 &&
   row stream16 300 python3 tools/bench_stream.py --conns 65536 --recs 16 &&
   row stream4 300 python3 tools/bench_stream.py --conns 65536 --recs 4 &&
   row stream16s 300 python3 tools/bench_stream.py --conns 65536 --recs 16 --content 1400 &&

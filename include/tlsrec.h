@@ -369,6 +369,81 @@ typedef struct tlsrec_tls13_secret {
 int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                tlsrec_tls13_secret *secrets, int key_update, void *stream);
 
+/* ---- TLS 1.2 / DTLS 1.2 key derivation (library/ssl_tls.c) ---------------
+ * The TLS 1.2 PRF (RFC 5246 section 5, P_SHA256 / P_SHA384) on the GPU: the
+ * reference's single-shot functions, and a batch that expands many
+ * connections' master secrets straight into a device key table -- the first
+ * half of ssl_tls12_populate_transform (ssl_tls.c:7750, :7858-7892), whose
+ * second half is tlsrec_transform_setup.  TLS 1.2 fixes the hash per suite,
+ * not per cipher (the *_SHA384 suites: AES-256-GCM, ARIA-256-GCM,
+ * Camellia-256-GCM; AES-256-CCM and ChaCha20-Poly1305 use SHA-256), so `prf`
+ * is explicit and every cipher works with either hash.
+ * Return codes: a prf of TLSREC_TLS_PRF_NONE or any unknown value is
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE (ssl_tls.c:465, decided before the GPU
+ * is touched), a device failure TLSREC_ERR_SSL_HW_ACCEL_FAILED.  The one
+ * divergence: the single-shot calls stage their inputs and output in a
+ * 32 KiB device arena, and a call that does not fit returns
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA (PSA has no such limit). */
+#define TLSREC_TLS_PRF_NONE    0   /* MBEDTLS_SSL_TLS_PRF_NONE,   ssl.h:1254 */
+#define TLSREC_TLS_PRF_SHA384  1   /* MBEDTLS_SSL_TLS_PRF_SHA384, ssl.h:1255 */
+#define TLSREC_TLS_PRF_SHA256  2   /* MBEDTLS_SSL_TLS_PRF_SHA256, ssl.h:1256 */
+#define TLSREC_IS_CLIENT 0         /* MBEDTLS_SSL_IS_CLIENT */
+#define TLSREC_IS_SERVER 1         /* MBEDTLS_SSL_IS_SERVER */
+
+/* mbedtls_ssl_tls_prf, ssl_tls.c:465 (RFC 5246 section 5: P_hash over label ||
+ * random; label is a C string).  slen == 0 is legal (ssl_tls.c:6117-6123);
+ * dlen == 0 returns 0 and writes nothing. */
+int tlsrec_tls_prf(int prf, const unsigned char *secret, size_t slen, const char *label,
+                   const unsigned char *random, size_t rlen, unsigned char *dstbuf, size_t dlen);
+
+/* ssl_compute_master, ssl_tls.c:6251 (non-PSK branch :6434): "master secret" over
+ * client_random || server_random, or with extended_ms != 0 "extended master secret"
+ * over the session hash (RFC 7627 section 4); master is 48 bytes */
+int tlsrec_tls12_compute_master(int prf, const unsigned char *premaster, size_t pmslen,
+                                const unsigned char *seed, size_t seed_len, int extended_ms,
+                                unsigned char master[48]);
+
+/* host-only, no GPU: the AEAD-branch split of the key block, ssl_tls.c:7858-7892
+ * (mac_key_len = 0): client_write_key | server_write_key | client_write_iv | server_write_iv,
+ * key_len = the cipher's, iv_len = fixed_ivlen (4 for GCM / CCM, 12 for ChaCha20-Poly1305).
+ * A block shorter than 2 * key_len + 2 * iv_len is TLSREC_ERR_SSL_BAD_INPUT_DATA, an
+ * unknown cipher TLSREC_ERR_SSL_FEATURE_UNAVAILABLE; unused bytes of `keys` are zero. */
+int tlsrec_tls12_split_key_block(int cipher, const unsigned char *keyblk, size_t keyblk_len,
+                                 tlsrec_key_set *keys);
+
+/* PRF(master, "key expansion", randbytes) + the split; randbytes = server_random ||
+ * client_random, i.e. handshake->randbytes after the swap at ssl_tls.c:6479-6488 */
+int tlsrec_tls12_make_keys(int prf, int cipher, const unsigned char master[48],
+                           const unsigned char randbytes[64], tlsrec_key_set *keys);
+
+/* mbedtls_ssl_tls12_export_keying_material, ssl_tls.c:8886 (RFC 5705); randbytes as above
+ * (the function un-swaps them, :8920-8925); context_len > 65535 -> BAD_INPUT_DATA */
+int tlsrec_tls12_export_keying_material(int prf, const unsigned char master[48],
+                                        const unsigned char randbytes[64],
+                                        const char *label, size_t label_len,
+                                        const unsigned char *context, size_t context_len,
+                                        int use_context, unsigned char *out, size_t out_len);
+
+/* One TLS 1.2 / DTLS 1.2 connection after its handshake, 112 bytes, device-resident */
+typedef struct tlsrec_tls12_conn {
+    uint8_t master[48];
+    uint8_t randbytes[64];   /* server_random || client_random */
+} tlsrec_tls12_conn;
+
+/* Batch: for each of `count` connections run the key expansion and load
+ * client_write into slot first + 2*i and server_write into slot first + 2*i + 1 of `kt`
+ * as TLS 1.2 keys of `cipher` (tls_minor 3, fixed_ivlen 4 or 12, the cipher's taglen;
+ * key expansion and GHASH tables as tlsrec_keytab_load).  A server endpoint
+ * encrypts with the odd slot and decrypts with the even one; a client does
+ * the reverse.  Asynchronous on `stream`; conns must stay valid until the
+ * stream reaches it, and is only read.  No host round trip.
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA: kt NULL, conns NULL with count != 0, or
+ * [first, first + 2*count) overflows or runs past the table;
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE: unknown cipher (as
+ * tlsrec_tls13_keytab_derive) or prf. */
+int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                               int prf, const tlsrec_tls12_conn *conns, void *stream);
+
 /* ---- TLS stream record layer --------------------------
  * Whole-connection framing on the device: received byte streams are split at
  * their 5-byte record headers, checked and decrypted in place; application

@@ -58,6 +58,8 @@ ALG_SHA_256 = 0x02000009      # PSA_ALG_SHA_256
 ALG_SHA_384 = 0x0200000a      # PSA_ALG_SHA_384
 TLS13_CONTEXT_UNHASHED = 0
 TLS13_CONTEXT_HASHED = 1
+TLS_PRF_NONE, TLS_PRF_SHA384, TLS_PRF_SHA256 = 0, 1, 2      # mbedtls_tls_prf_types, ssl.h:1254-1256
+IS_CLIENT, IS_SERVER = 0, 1                                 # MBEDTLS_SSL_IS_CLIENT / _SERVER
 
 # ---- layouts -----------------------------------------------------------------
 KEY_MATERIAL = np.dtype([("cipher", "u1"), ("tls_minor", "u1"), ("fixed_ivlen", "u1"),
@@ -115,6 +117,11 @@ class CKeySet(ctypes.Structure):
                 ("key_len", ctypes.c_size_t), ("iv_len", ctypes.c_size_t)]
 
 
+class CTls12Conn(ctypes.Structure):
+    """tlsrec_tls12_conn: one TLS 1.2 / DTLS 1.2 connection after its handshake (112 bytes)"""
+    _fields_ = [("master", ctypes.c_ubyte * 48), ("randbytes", ctypes.c_ubyte * 64)]
+
+
 class CTicketKeys(ctypes.Structure):
     """the keys[2] / active fields of mbedtls_ssl_ticket_context"""
     _fields_ = [("slot", ctypes.c_uint32 * 2), ("name", (ctypes.c_uint8 * 4) * 2), ("active", ctypes.c_uint32)]
@@ -157,6 +164,12 @@ SIGNATURES = {
     "tlsrec_tls13_exporter": (_INT, [_INT, _VP, _SZ, _VP, _SZ, _VP, _SZ, _VP, _SZ]),
     "tlsrec_tls13_update_traffic_secret": (_INT, [_INT, _VP, _VP]),
     "tlsrec_tls13_keytab_derive": (_INT, [_VP, _U32, _U32, _INT, _VP, _INT, _VP]),
+    "tlsrec_tls_prf": (_INT, [_INT, _VP, _SZ, ctypes.c_char_p, _VP, _SZ, _VP, _SZ]),
+    "tlsrec_tls12_compute_master": (_INT, [_INT, _VP, _SZ, _VP, _SZ, _INT, _VP]),
+    "tlsrec_tls12_split_key_block": (_INT, [_INT, _VP, _SZ, _VP]),
+    "tlsrec_tls12_make_keys": (_INT, [_INT, _INT, _VP, _VP, _VP]),
+    "tlsrec_tls12_export_keying_material": (_INT, [_INT, _VP, _VP, _VP, _SZ, _VP, _SZ, _INT, _VP, _SZ]),
+    "tlsrec_tls12_keytab_derive": (_INT, [_VP, _U32, _U32, _INT, _INT, _VP, _VP]),
     "tlsrec_ticket_write": (_INT, [_VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_ticket_parse": (_INT, [_VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_stream_decrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),

@@ -21,6 +21,12 @@
  * derivation: this is per-connection control work (a few SHA compressions),
  * not the bulk path, so lanes are independent and the message buffers live
  * in per-lane scratch.
+ *
+ * Also the TLS 1.2 / DTLS 1.2 key derivation of library/ssl_tls.c (the PRF of
+ * RFC 5246 section 5; table at the host section below): the single-shot calls
+ * as one more job of the same kernel, and a batch, tlsrec_tls12_keytab_derive,
+ * whose kernel is written for its fixed shapes (word-oriented SHA-2 in
+ * registers, HMAC midstates reused) instead of the byte-wise path above.
  */
 #include <hip/hip_runtime.h>
 #include <pthread.h>
@@ -253,8 +259,42 @@ __device__ void hkdf_expand(uint32_t alg, const uint8_t *prk, uint32_t prk_len, 
     }
 }
 
+/* TLS 1.2 PRF (RFC 5246 5, tls_prf_generic ssl_tls.c:6099) with seed = label || random:
+ * A(0) = seed, A(i) = HMAC(secret, A(i-1)), out = HMAC(secret, A(1) || seed) || HMAC(secret, A(2) || seed) ... */
+__device__ void tls_prf(uint32_t alg, const uint8_t *secret, uint32_t slen, const uint8_t *label, uint32_t llen,
+                        const uint8_t *rnd, uint32_t rlen, uint8_t *out, uint32_t out_len)
+{
+    const uint32_t H = out_bytes(alg);
+    uint8_t a[48], t[48];
+    {
+        Hmac m;
+        hmac_start(m, alg, secret, slen);
+        update(m.in, label, llen);
+        update(m.in, rnd, rlen);
+        hmac_end(m, a);
+    }
+    uint32_t done = 0;
+    while (done < out_len) {
+        Hmac m;
+        hmac_start(m, alg, secret, slen);
+        update(m.in, a, H);
+        update(m.in, label, llen);
+        update(m.in, rnd, rlen);
+        hmac_end(m, t);
+        const uint32_t take = out_len - done < H ? out_len - done : H;
+        for (uint32_t j = 0; j < take; j++) out[done + j] = t[j];
+        done += take;
+        if (done < out_len) {
+            Hmac n;
+            hmac_start(n, alg, secret, slen);
+            update(n.in, a, H);
+            hmac_end(n, a);
+        }
+    }
+}
+
 /* ---------------- kernels ---------------------------------------------- */
-enum { OP_HASH = 0, OP_HMAC = 1, OP_EXPAND = 2 };
+enum { OP_HASH = 0, OP_HMAC = 1, OP_EXPAND = 2, OP_PRF = 3 };
 
 struct Job {
     uint32_t op, alg;
@@ -285,6 +325,8 @@ __global__ void __launch_bounds__(64) kdf_job_kernel(const Job *jobs, uint32_t n
         update(m.in, j.msg, j.msg_len);
         update(m.in, j.msg2, j.msg2_len);
         hmac_end(m, j.out);
+    } else if (j.op == OP_PRF) {
+        tls_prf(j.alg, j.key, j.key_len, j.msg, j.msg_len, j.msg2, j.msg2_len, j.out, j.out_len);
     } else {
         hkdf_expand(j.alg, j.key, j.key_len, j.msg, j.msg_len, j.msg2, j.msg2_len, j.out, j.out_len);
     }
@@ -335,6 +377,353 @@ __global__ void __launch_bounds__(64) tls13_derive_kernel(DeriveArgs a)
     const uint4 *src = reinterpret_cast<const uint4 *>(&km);
 #pragma unroll
     for (int k = 0; k < 4; k++) dst[k] = src[k];
+}
+
+/* ---------------- TLS 1.2 batch key expansion ---------------------------
+ * PRF(master, "key expansion", server_random || client_random) for one
+ * connection per lane.  Every shape is fixed (48-byte key, 77-byte seed, at
+ * most 88 bytes out), so nothing here goes through Hash / put(): the message
+ * blocks are assembled as big-endian words with their padding and length
+ * words as constants, the compression works on a 16-word window and 8 state
+ * words held in registers, and the two HMAC midstates (key ^ ipad, key ^
+ * opad) are computed once and reused by every HMAC of the chain.
+ *
+ * Compressions per connection, n = ceil(out_len / H):
+ *   SHA-256: 2 midstates, A(1) 3 (seed 77 B: two inner blocks + outer),
+ *            A(i>1) 2, each output block 3 (A || seed = 109 B)  -> 5n + 3
+ *   SHA-384: 2 midstates, A(i) 2, each output block 3 (A || seed = 125 B:
+ *            the padding spills into a second, constant block)  -> 5n + 2 */
+struct S256 {
+    typedef uint32_t W;
+    enum { ROUNDS = 64 };
+    static __device__ __forceinline__ W k(int i) { return kK256[i]; }
+    static __device__ __forceinline__ W S0(W x) { return ror32(x, 2) ^ ror32(x, 13) ^ ror32(x, 22); }
+    static __device__ __forceinline__ W S1(W x) { return ror32(x, 6) ^ ror32(x, 11) ^ ror32(x, 25); }
+    static __device__ __forceinline__ W s0(W x) { return ror32(x, 7) ^ ror32(x, 18) ^ (x >> 3); }
+    static __device__ __forceinline__ W s1(W x) { return ror32(x, 17) ^ ror32(x, 19) ^ (x >> 10); }
+};
+struct S512 {
+    typedef uint64_t W;
+    enum { ROUNDS = 80 };
+    static __device__ __forceinline__ W k(int i) { return kK512[i]; }
+    static __device__ __forceinline__ W S0(W x) { return ror64(x, 28) ^ ror64(x, 34) ^ ror64(x, 39); }
+    static __device__ __forceinline__ W S1(W x) { return ror64(x, 14) ^ ror64(x, 18) ^ ror64(x, 41); }
+    static __device__ __forceinline__ W s0(W x) { return ror64(x, 1) ^ ror64(x, 8) ^ (x >> 7); }
+    static __device__ __forceinline__ W s1(W x) { return ror64(x, 19) ^ ror64(x, 61) ^ (x >> 6); }
+};
+
+/* One round with the working variables rotated by the (compile-time) round
+ * index instead of moved: v[(0 - i) & 7] is a, ..., v[(7 - i) & 7] is h. */
+template <class T> __device__ __forceinline__ void sha_round(typename T::W (&v)[8], int i, typename T::W kw)
+{
+    typedef typename T::W W;
+    const W a = v[(0 - i) & 7], b = v[(1 - i) & 7], c = v[(2 - i) & 7];
+    const W e = v[(4 - i) & 7], f = v[(5 - i) & 7], g = v[(6 - i) & 7];
+    const W t1 = v[(7 - i) & 7] + T::S1(e) + (g ^ (e & (f ^ g))) + kw;
+    const W t2 = T::S0(a) + ((a & b) | (c & (a | b)));
+    v[(3 - i) & 7] += t1;
+    v[(7 - i) & 7] = t1 + t2;
+}
+
+/* FIPS 180-4 6.2.2 / 6.4.2 on one block: 16 rounds unrolled per trip so that
+ * every index into w[] and v[] is a constant (registers, no scratch), the
+ * trips themselves rolled to keep the code of one call site to 16 rounds.
+ * w[] is consumed (it becomes the last 16 schedule words). */
+template <class T> __device__ __forceinline__ void sha_compress(typename T::W (&st)[8], typename T::W (&w)[16])
+{
+    typename T::W v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) v[i] = st[i];
+#pragma unroll
+    for (int i = 0; i < 16; i++) sha_round<T>(v, i, T::k(i) + w[i]);
+#pragma unroll 1
+    for (int r = 16; r < T::ROUNDS; r += 16) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            w[i] += T::s0(w[(i + 1) & 15]) + w[(i + 9) & 15] + T::s1(w[(i + 14) & 15]);
+            sha_round<T>(v, i, T::k(r + i) + w[i]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] += v[i];
+}
+
+/* a big-endian 32-bit word of device memory, by one aligned load or by bytes */
+__device__ __forceinline__ uint32_t load_be32(const uint8_t *p, bool aligned)
+{
+    if (aligned) return __builtin_bswap32(*reinterpret_cast<const uint32_t *>(p));
+    return ((uint32_t) p[0] << 24) | ((uint32_t) p[1] << 16) | ((uint32_t) p[2] << 8) | p[3];
+}
+
+/* The 77-byte seed "key expansion" || randbytes as big-endian words: the
+ * 13-byte label leaves the random words one byte off, S[3 + k] =
+ * R[k-1] << 24 | R[k] >> 8; S[19] holds the last byte and the 0x80 that
+ * follows the seed wherever it ends a message. */
+__device__ __forceinline__ void tls12_seed_words(const uint32_t (&R)[16], uint32_t (&S)[20])
+{
+    S[0] = 0x6b657920u;      /* "key " */
+    S[1] = 0x65787061u;      /* "expa" */
+    S[2] = 0x6e73696fu;      /* "nsio" */
+    S[3] = 0x6e000000u | (R[0] >> 8);   /* "n" */
+#pragma unroll
+    for (int k = 1; k < 16; k++) S[3 + k] = (R[k - 1] << 24) | (R[k] >> 8);
+    S[19] = (R[15] << 24) | 0x00800000u;
+}
+
+/* P_SHA256: KB receives 8 words per iteration, ITERS = ceil(out_len / 32) */
+template <int ITERS>
+__device__ __forceinline__ void tls12_expand_sha256(const uint32_t (&M)[12], const uint32_t (&R)[16],
+                                                    uint32_t (&KB)[24])
+{
+    const uint32_t iv[8] = { 0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                             0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u };
+    const uint32_t HMAC_LEN = (64 + 32) * 8;     /* bits of key block || 32-byte digest */
+    uint32_t S[20], w[16], ip[8], op[8], st[8], A[8];
+    tls12_seed_words(R, S);
+    /* midstates: one block of master ^ pad, master zero-padded to 64 bytes (RFC 2104) */
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = (j < 12 ? M[j] : 0u) ^ 0x36363636u;
+#pragma unroll
+    for (int j = 0; j < 8; j++) ip[j] = iv[j];
+    sha_compress<S256>(ip, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = (j < 12 ? M[j] : 0u) ^ 0x5c5c5c5cu;
+#pragma unroll
+    for (int j = 0; j < 8; j++) op[j] = iv[j];
+    sha_compress<S256>(op, w);
+    /* outer hash of an HMAC: opad midstate over the 32-byte inner digest in st */
+    auto outer = [&](uint32_t (&dst)[8]) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = st[j];
+        w[8] = 0x80000000u;
+#pragma unroll
+        for (int j = 9; j < 15; j++) w[j] = 0;
+        w[15] = HMAC_LEN;
+#pragma unroll
+        for (int j = 0; j < 8; j++) dst[j] = op[j];
+        sha_compress<S256>(dst, w);
+    };
+#pragma unroll
+    for (int j = 0; j < 8; j++) A[j] = 0;
+#pragma unroll 1
+    for (int it = 0; it < ITERS; it++) {
+        /* A(it + 1) = HMAC(A(it)); A(0) is the seed, whose 77 bytes take a second block */
+        const bool first = it == 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = first ? S[j] : A[j];
+        w[8] = first ? S[8] : 0x80000000u;
+#pragma unroll
+        for (int j = 9; j < 15; j++) w[j] = first ? S[j] : 0u;
+        w[15] = first ? S[15] : HMAC_LEN;
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        sha_compress<S256>(st, w);
+        if (first) {
+            w[0] = S[16]; w[1] = S[17]; w[2] = S[18]; w[3] = S[19];
+#pragma unroll
+            for (int j = 4; j < 15; j++) w[j] = 0;
+            w[15] = (64 + 77) * 8;
+            sha_compress<S256>(st, w);
+        }
+        outer(A);
+        /* output block = HMAC(A || seed): 109 bytes, 64 + 45 */
+#pragma unroll
+        for (int j = 0; j < 8; j++) { w[j] = A[j]; w[8 + j] = S[j]; }
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        sha_compress<S256>(st, w);
+#pragma unroll
+        for (int j = 0; j < 12; j++) w[j] = S[8 + j];
+        w[12] = 0; w[13] = 0; w[14] = 0;
+        w[15] = (64 + 109) * 8;
+        sha_compress<S256>(st, w);
+        uint32_t D[8];
+        outer(D);
+#pragma unroll
+        for (int q = 0; q < ITERS; q++) {
+            if (it == q) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) KB[8 * q + j] = D[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) D[j] = 0;
+    }
+    /* the reference zeroizes keyblk and the PSA operation; nothing of the chain stays behind */
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; st[j] = 0; A[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 20; j++) S[j] = 0;
+}
+
+/* P_SHA384 (SHA-512 compression, 128-byte blocks, 48-byte digests): KB
+ * receives 12 words per iteration, ITERS = ceil(out_len / 48) */
+template <int ITERS>
+__device__ __forceinline__ void tls12_expand_sha384(const uint32_t (&M)[12], const uint32_t (&R)[16],
+                                                    uint32_t (&KB)[24])
+{
+    const uint64_t iv[8] = { 0xcbbb9d5dc1059ed8ULL, 0x629a292a367cd507ULL, 0x9159015a3070dd17ULL,
+                             0x152fecd8f70e5939ULL, 0x67332667ffc00b31ULL, 0x8eb44a8768581511ULL,
+                             0xdb0c2e0d64f98fa7ULL, 0x47b5481dbefa4fa4ULL };
+    const uint64_t HMAC_LEN = (128 + 48) * 8;
+    uint32_t S[20];
+    uint64_t T[10], w[16], ip[8], op[8], st[8], A[6];
+    tls12_seed_words(R, S);
+#pragma unroll
+    for (int j = 0; j < 10; j++) T[j] = ((uint64_t) S[2 * j] << 32) | S[2 * j + 1];   /* T[9]: 5 seed bytes, 0x80 */
+#pragma unroll
+    for (int j = 0; j < 16; j++)
+        w[j] = (j < 6 ? (((uint64_t) M[2 * j] << 32) | M[2 * j + 1]) : 0ULL) ^ 0x3636363636363636ULL;
+#pragma unroll
+    for (int j = 0; j < 8; j++) ip[j] = iv[j];
+    sha_compress<S512>(ip, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++)
+        w[j] = (j < 6 ? (((uint64_t) M[2 * j] << 32) | M[2 * j + 1]) : 0ULL) ^ 0x5c5c5c5c5c5c5c5cULL;
+#pragma unroll
+    for (int j = 0; j < 8; j++) op[j] = iv[j];
+    sha_compress<S512>(op, w);
+    /* outer hash: opad midstate over the first 48 bytes of st; the first 6 words of the result */
+    auto outer = [&](uint64_t (&dst)[6]) {
+        uint64_t o[8];
+#pragma unroll
+        for (int j = 0; j < 6; j++) w[j] = st[j];
+        w[6] = 0x8000000000000000ULL;
+#pragma unroll
+        for (int j = 7; j < 15; j++) w[j] = 0;
+        w[15] = HMAC_LEN;
+#pragma unroll
+        for (int j = 0; j < 8; j++) o[j] = op[j];
+        sha_compress<S512>(o, w);
+#pragma unroll
+        for (int j = 0; j < 6; j++) dst[j] = o[j];
+#pragma unroll
+        for (int j = 0; j < 8; j++) o[j] = 0;
+    };
+#pragma unroll
+    for (int j = 0; j < 6; j++) A[j] = 0;
+#pragma unroll 1
+    for (int it = 0; it < ITERS; it++) {
+        /* A(it + 1) = HMAC(A(it)): the 77-byte seed or a 48-byte digest, one block either way */
+        const bool first = it == 0;
+#pragma unroll
+        for (int j = 0; j < 6; j++) w[j] = first ? T[j] : A[j];
+        w[6] = first ? T[6] : 0x8000000000000000ULL;
+#pragma unroll
+        for (int j = 7; j < 10; j++) w[j] = first ? T[j] : 0ULL;
+#pragma unroll
+        for (int j = 10; j < 15; j++) w[j] = 0;
+        w[15] = first ? (uint64_t) ((128 + 77) * 8) : HMAC_LEN;
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        sha_compress<S512>(st, w);
+        outer(A);
+        /* output block = HMAC(A || seed): 125 bytes fill the block up to its last
+         * 3 bytes, so the 0x80 is in T[9] and the length goes to a second block */
+#pragma unroll
+        for (int j = 0; j < 6; j++) w[j] = A[j];
+#pragma unroll
+        for (int j = 0; j < 10; j++) w[6 + j] = T[j];
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        sha_compress<S512>(st, w);
+#pragma unroll
+        for (int j = 0; j < 15; j++) w[j] = 0;
+        w[15] = (128 + 125) * 8;
+        sha_compress<S512>(st, w);
+        uint64_t D[6];
+        outer(D);
+#pragma unroll
+        for (int q = 0; q < ITERS; q++) {
+            if (it == q) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) {
+                    KB[12 * q + 2 * j] = (uint32_t) (D[j] >> 32);
+                    KB[12 * q + 2 * j + 1] = (uint32_t) D[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++) D[j] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; st[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 6; j++) A[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 10; j++) T[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 20; j++) S[j] = 0;
+}
+
+struct Tls12Args {
+    const tlsrec_tls12_conn *conns;
+    tlsrec_key_material *out;     /* staging area of slot `first`: 2 records per connection */
+    uint32_t count, cipher, taglen, aligned;
+};
+
+/* One lane per connection; KL / IVL = the cipher's key length and TLS 1.2
+ * fixed_ivlen, so the split of the key block (ssl_tls.c:7858-7892) indexes
+ * registers with constants. */
+template <int ALG, int KL, int IVL> __global__ void __launch_bounds__(64) tls12_derive_kernel(Tls12Args a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    constexpr int OUT = 2 * KL + 2 * IVL, H = ALG == H_SHA384 ? 48 : 32, ITERS = (OUT + H - 1) / H;
+    static_assert(ITERS * H <= 96 && KL % 4 == 0 && IVL % 4 == 0, "key block shape");
+    const uint8_t *c = reinterpret_cast<const uint8_t *>(a.conns + i);
+    const bool aligned = a.aligned != 0;
+    uint32_t M[12], R[16], KB[24];
+    if (aligned) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(c);
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const uint4 v = q[k];
+            const uint32_t x[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int n = 4 * k + j;
+                if (n < 12) M[n] = __builtin_bswap32(x[j]);
+                else R[n - 12] = __builtin_bswap32(x[j]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < 12; n++) M[n] = load_be32(c + 4 * n, false);
+#pragma unroll
+        for (int n = 0; n < 16; n++) R[n] = load_be32(c + 48 + 4 * n, false);
+    }
+#pragma unroll
+    for (int j = 0; j < 24; j++) KB[j] = 0;
+    if constexpr (ALG == H_SHA384) tls12_expand_sha384<ITERS>(M, R, KB);
+    else tls12_expand_sha256<ITERS>(M, R, KB);
+    /* tlsrec_key_material: cipher, tls_minor 3, fixed_ivlen, taglen | granularity 0, reserved |
+     * iv[16] | key[32]; client_write first, then server_write */
+    const uint32_t head = a.cipher | (3u << 8) | ((uint32_t) IVL << 16) | (a.taglen << 24);
+    uint4 *dst = reinterpret_cast<uint4 *>(a.out + 2 * (size_t) i);
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+        uint32_t km[16];
+        km[0] = head;
+#pragma unroll
+        for (int j = 1; j < 16; j++) km[j] = 0;
+#pragma unroll
+        for (int j = 0; j < IVL / 4; j++) km[4 + j] = __builtin_bswap32(KB[2 * KL / 4 + side * (IVL / 4) + j]);
+#pragma unroll
+        for (int j = 0; j < KL / 4; j++) km[8 + j] = __builtin_bswap32(KB[side * (KL / 4) + j]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) dst[4 * side + k] = make_uint4(km[4 * k], km[4 * k + 1], km[4 * k + 2], km[4 * k + 3]);
+#pragma unroll
+        for (int j = 0; j < 16; j++) km[j] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < 24; j++) KB[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 12; j++) M[j] = 0;
 }
 
 } /* namespace tlsks */
@@ -653,8 +1042,11 @@ extern "C" tlsrec_key_material *tlsrec__keytab_stage(tlsrec_keytab *kt);
 extern "C" int tlsrec__keytab_commit_staged(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                             hipStream_t st);
 
-extern "C" int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
-                                          tlsrec_tls13_secret *secrets, int key_update, void *stream)
+/* The derive kernel alone: key material of `count` slots into the staging
+ * area, nothing committed (tools/bench_keysched.py times it apart from the
+ * key setup; tlsrec_tls13_keytab_derive is this + the commit). */
+extern "C" int tlsrec__tls13_stage_keys(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                        tlsrec_tls13_secret *secrets, int key_update, void *stream)
 {
     if (!kt || (!secrets && count)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (first > tlsrec_keytab_capacity(kt) || count > tlsrec_keytab_capacity(kt) - first)
@@ -685,7 +1077,201 @@ extern "C" int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uin
     a.key_len = key_len;
     a.update = key_update ? 1u : 0u;
     hipLaunchKernelGGL(tls13_derive_kernel, dim3((count + 63) / 64), dim3(64), 0, st, a);
-    int r = hipGetLastError() == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    if (r == 0) r = tlsrec__keytab_commit_staged(kt, first, count, cipher, st);
+    return hipGetLastError() == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                          tlsrec_tls13_secret *secrets, int key_update, void *stream)
+{
+    int r = tlsrec__tls13_stage_keys(kt, first, count, cipher, secrets, key_update, stream);
+    if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, count, cipher, (hipStream_t) stream);
+    return r;
+}
+
+/* ======================================================================
+ * TLS 1.2 / DTLS 1.2 (library/ssl_tls.c)
+ *
+ *   reference                                        here
+ *   mbedtls_ssl_tls_prf               :465           tlsrec_tls_prf
+ *   tls_prf_generic                   :6099          OP_PRF (tls_prf() above)
+ *   ssl_compute_master                :6251-6451     tlsrec_tls12_compute_master (non-PSK branch)
+ *   key-block split                   :7858-7892     tlsrec_tls12_split_key_block (host only)
+ *   tls_prf(.., "key expansion", ..)  :7750          tlsrec_tls12_make_keys
+ *   mbedtls_ssl_tls12_export_keying_material :8886   tlsrec_tls12_export_keying_material
+ *   (batch)                                          tlsrec_tls12_keytab_derive
+ * ==================================================================== */
+static int prf_index(int prf)
+{
+    return prf == TLSREC_TLS_PRF_SHA256 ? H_SHA256 : prf == TLSREC_TLS_PRF_SHA384 ? H_SHA384 : -1;
+}
+
+/* fixed_ivlen of a TLS 1.2 AEAD transform, ssl_tls.c:7722-7727 */
+static size_t tls12_fixed_ivlen(int cipher) { return cipher == TLSREC_CIPHER_CHACHA20_POLY1305 ? 12 : 4; }
+
+static void wipe(void *p, size_t n)
+{
+    volatile uint8_t *v = (volatile uint8_t *) p;
+    for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
+/* PRF with seed = label || r1 || r2 through the arena (a = H_SHA256 / H_SHA384) */
+static int prf_run(int a, const unsigned char *secret, size_t slen, const char *label, size_t llen,
+                   const unsigned char *r1, size_t r1len, const unsigned char *r2, size_t r2len,
+                   unsigned char *dst, size_t dlen)
+{
+    if ((slen && !secret) || (llen && !label) || (r1len && !r1) || (r2len && !r2) || !dst)
+        return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    /* the arena holds the secret, the label, the random bytes and the output, each rounded to 16 bytes */
+    const size_t lim = 32768;
+    if (slen > lim || llen > lim || r1len > lim || r2len > lim || dlen > lim) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const size_t rlen = r1len + r2len;
+    if (((slen + 15) & ~(size_t) 15) + ((llen + 15) & ~(size_t) 15) + ((rlen + 15) & ~(size_t) 15) +
+        ((dlen + 15) & ~(size_t) 15) > lim)
+        return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    Arena ar;
+    const size_t o_sec = ar.put(secret, slen), o_lab = ar.put(label, llen);
+    const size_t o_rnd = ar.used;
+    if (r1len) memcpy(ar.host + o_rnd, r1, r1len);
+    if (r2len) memcpy(ar.host + o_rnd + r1len, r2, r2len);
+    ar.used = (ar.used + rlen + 15) & ~(size_t) 15;
+    const size_t o_out = ar.put(nullptr, dlen);
+    Job j[1] = { job(OP_PRF, a, o_sec, (uint32_t) slen, o_lab, (uint32_t) llen, o_out, (uint32_t) dlen) };
+    j[0].msg2 = dev_off(o_rnd);
+    j[0].msg2_len = (uint32_t) rlen;
+    const int first[2] = { 0, 1 };
+    void *ho[1] = { dst };
+    return run_jobs(ar, j, first, 1, &o_out, ho, &dlen, 1);
+}
+
+extern "C" int tlsrec_tls_prf(int prf, const unsigned char *secret, size_t slen, const char *label,
+                              const unsigned char *random, size_t rlen, unsigned char *dstbuf, size_t dlen)
+{
+    const int a = prf_index(prf);
+    if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;      /* ssl_tls.c:489-490 */
+    if (dlen == 0) return 0;
+    if (!label) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    return prf_run(a, secret, slen, label, strlen(label), random, rlen, nullptr, 0, dstbuf, dlen);
+}
+
+extern "C" int tlsrec_tls12_compute_master(int prf, const unsigned char *premaster, size_t pmslen,
+                                           const unsigned char *seed, size_t seed_len, int extended_ms,
+                                           unsigned char master[48])
+{
+    const int a = prf_index(prf);
+    if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    /* ssl_tls.c:6269, :6295 */
+    const char *lbl = extended_ms ? "extended master secret" : "master secret";
+    return prf_run(a, premaster, pmslen, lbl, strlen(lbl), seed, seed_len, nullptr, 0, master, 48);
+}
+
+extern "C" int tlsrec_tls12_split_key_block(int cipher, const unsigned char *keyblk, size_t keyblk_len,
+                                            tlsrec_key_set *keys)
+{
+    if (!keys || !keyblk) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const size_t kl = tlsrec_cipher_keylen(cipher);
+    if (kl == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    const size_t il = tls12_fixed_ivlen(cipher);
+    if (keyblk_len < 2 * kl + 2 * il) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    memset(keys, 0, sizeof(*keys));
+    /* ssl_tls.c:7858-7892 with mac_key_len = 0: key1 = keyblk, key2 = key1 + keylen,
+     * the IVs follow; the client writes with key1 / the first IV */
+    memcpy(keys->client_write_key, keyblk, kl);
+    memcpy(keys->server_write_key, keyblk + kl, kl);
+    memcpy(keys->client_write_iv, keyblk + 2 * kl, il);
+    memcpy(keys->server_write_iv, keyblk + 2 * kl + il, il);
+    keys->key_len = kl;
+    keys->iv_len = il;
+    return 0;
+}
+
+extern "C" int tlsrec_tls12_make_keys(int prf, int cipher, const unsigned char master[48],
+                                      const unsigned char randbytes[64], tlsrec_key_set *keys)
+{
+    const int a = prf_index(prf);
+    if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    const size_t kl = tlsrec_cipher_keylen(cipher);
+    if (kl == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (!master || !randbytes || !keys) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    /* the reference expands 256 bytes (ssl_tls.c:7750) and uses this prefix of them */
+    unsigned char keyblk[96];
+    const size_t need = 2 * kl + 2 * tls12_fixed_ivlen(cipher);
+    int r = prf_run(a, master, 48, "key expansion", 13, randbytes, 64, nullptr, 0, keyblk, need);
+    if (r == 0) r = tlsrec_tls12_split_key_block(cipher, keyblk, need, keys);
+    wipe(keyblk, sizeof(keyblk));
+    return r;
+}
+
+extern "C" int tlsrec_tls12_export_keying_material(int prf, const unsigned char master[48],
+                                                   const unsigned char randbytes[64], const char *label,
+                                                   size_t label_len, const unsigned char *context,
+                                                   size_t context_len, int use_context, unsigned char *out,
+                                                   size_t out_len)
+{
+    const int a = prf_index(prf);
+    if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (use_context && context_len > 65535) return TLSREC_ERR_SSL_BAD_INPUT_DATA;     /* ssl_tls.c:8905 */
+    if (out_len == 0) return 0;
+    if (!master || !randbytes || (use_context && context_len && !context)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    /* client_random || server_random [|| uint16 context_len || context], ssl_tls.c:8920-8929 */
+    unsigned char head[66];
+    memcpy(head, randbytes + 32, 32);
+    memcpy(head + 32, randbytes, 32);
+    head[64] = (unsigned char) (context_len >> 8);
+    head[65] = (unsigned char) context_len;
+    return prf_run(a, master, 48, label, label_len, head, use_context ? 66 : 64, context,
+                   use_context ? context_len : 0, out, out_len);
+}
+
+template <int ALG, int KL, int IVL> static hipError_t tls12_launch(const Tls12Args &a, hipStream_t st)
+{
+    hipLaunchKernelGGL((tls12_derive_kernel<ALG, KL, IVL>), dim3((a.count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+static int tls12_check(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int prf,
+                       const tlsrec_tls12_conn *conns)
+{
+    if (!kt || (!conns && count)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const uint32_t cap = tlsrec_keytab_capacity(kt);
+    if (first > cap || (uint64_t) count * 2 > (uint64_t) (cap - first)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (tlsrec_cipher_keylen(cipher) == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (prf_index(prf) < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    return 0;
+}
+
+/* The derive kernel alone (see tlsrec__tls13_stage_keys). */
+extern "C" int tlsrec__tls12_stage_keys(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int prf,
+                                        const tlsrec_tls12_conn *conns, void *stream)
+{
+    int r = tls12_check(kt, first, count, cipher, prf, conns);
+    if (r != 0 || count == 0) return r;
+    const int alg = prf_index(prf);
+    const uint32_t kl = tlsrec_cipher_keylen(cipher);
+    Tls12Args a;
+    a.conns = conns;
+    a.out = tlsrec__keytab_stage(kt) + first;
+    a.count = count;
+    a.cipher = (uint32_t) cipher;
+    a.taglen = tlsrec_cipher_taglen(cipher);
+    a.aligned = ((uintptr_t) conns & 15) == 0;     /* 112-byte records: 16-byte loads if the array is aligned */
+    hipStream_t st = (hipStream_t) stream;
+    hipError_t e;
+    if (alg == H_SHA384) {
+        e = cipher == TLSREC_CIPHER_CHACHA20_POLY1305 ? tls12_launch<H_SHA384, 32, 12>(a, st)
+            : kl == 16 ? tls12_launch<H_SHA384, 16, 4>(a, st)
+            : kl == 24 ? tls12_launch<H_SHA384, 24, 4>(a, st) : tls12_launch<H_SHA384, 32, 4>(a, st);
+    } else {
+        e = cipher == TLSREC_CIPHER_CHACHA20_POLY1305 ? tls12_launch<H_SHA256, 32, 12>(a, st)
+            : kl == 16 ? tls12_launch<H_SHA256, 16, 4>(a, st)
+            : kl == 24 ? tls12_launch<H_SHA256, 24, 4>(a, st) : tls12_launch<H_SHA256, 32, 4>(a, st);
+    }
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int prf,
+                                          const tlsrec_tls12_conn *conns, void *stream)
+{
+    int r = tlsrec__tls12_stage_keys(kt, first, count, cipher, prf, conns, stream);
+    if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, 2 * count, cipher, (hipStream_t) stream);
     return r;
 }

@@ -1,0 +1,103 @@
+"""TLS 1.2 / DTLS 1.2 key derivation on the GPU (library/ssl_tls.c), through
+the C ABI of include/tlsrec.h.  Same arguments, outputs and error codes as the
+reference functions; the PRF (RFC 5246 section 5) runs in HIP kernels.
+
+    mbedtls_ssl_tls_prf                       (:465)   -> tls_prf
+    ssl_compute_master, non-PSK branch        (:6251)  -> tls12_compute_master
+    key-block split, AEAD branch              (:7858)  -> tls12_split_key_block (host only)
+    tls_prf(.., "key expansion", ..) + split  (:7750)  -> tls12_make_keys
+    mbedtls_ssl_tls12_export_keying_material  (:8886)  -> tls12_export_keying_material
+    batch: master secrets in HBM -> key-table slots    -> tls12_keytab_derive
+
+`prf` is explicit (TLS 1.2 fixes the hash per suite, not per cipher); errors
+raise KeyScheduleError with the reference's code.
+"""
+from __future__ import annotations
+
+import ctypes
+
+from . import _abi
+from .batch import KeyTable, _ptr, _stream
+from .keysched import KeyScheduleError, _b, _chk
+
+PRF_NONE = _abi.TLS_PRF_NONE
+PRF_SHA384 = _abi.TLS_PRF_SHA384
+PRF_SHA256 = _abi.TLS_PRF_SHA256
+IS_CLIENT = _abi.IS_CLIENT
+IS_SERVER = _abi.IS_SERVER
+CONN_BYTES = ctypes.sizeof(_abi.CTls12Conn)      # master[48] || server_random[32] || client_random[32]
+
+__all__ = ["PRF_NONE", "PRF_SHA384", "PRF_SHA256", "IS_CLIENT", "IS_SERVER", "CONN_BYTES", "KeyScheduleError",
+           "tls_prf", "tls12_compute_master", "tls12_split_key_block", "tls12_make_keys",
+           "tls12_export_keying_material", "tls12_keytab_derive", "tls12_slots"]
+
+
+def _key_set(ks):
+    kl, il = ks.key_len, ks.iv_len
+    return (bytes(ks.client_write_key[:kl]), bytes(ks.client_write_iv[:il]),
+            bytes(ks.server_write_key[:kl]), bytes(ks.server_write_iv[:il]))
+
+
+def tls_prf(prf: int, secret: bytes, label: bytes, random: bytes, n: int) -> bytes:
+    """`label` is passed as a C string (no NUL inside), as the reference takes it."""
+    out = ctypes.create_string_buffer(max(1, n))
+    _chk("tlsrec_tls_prf", _abi.load().tlsrec_tls_prf(prf, _b(secret), len(secret), bytes(label), _b(random),
+                                                      len(random), out, n))
+    return out.raw[:n]
+
+
+def tls12_compute_master(prf: int, premaster: bytes, seed: bytes, extended_ms: bool = False) -> bytes:
+    """`seed`: client_random || server_random, or the session hash when extended_ms."""
+    out = ctypes.create_string_buffer(48)
+    _chk("tlsrec_tls12_compute_master", _abi.load().tlsrec_tls12_compute_master(
+        prf, _b(premaster), len(premaster), _b(seed), len(seed), int(bool(extended_ms)), out))
+    return out.raw
+
+
+def tls12_split_key_block(cipher: int, keyblk: bytes):
+    """(client_write_key, client_write_iv, server_write_key, server_write_iv); needs no GPU."""
+    ks = _abi.CKeySet()
+    _chk("tlsrec_tls12_split_key_block", _abi.load().tlsrec_tls12_split_key_block(
+        cipher, _b(keyblk), len(keyblk), ctypes.byref(ks)))
+    return _key_set(ks)
+
+
+def tls12_make_keys(prf: int, cipher: int, master: bytes, randbytes: bytes):
+    """`randbytes`: server_random || client_random (handshake->randbytes after the swap)."""
+    if len(master) != 48 or len(randbytes) != 64:
+        raise KeyScheduleError("tlsrec_tls12_make_keys", _abi.ERR_SSL_BAD_INPUT_DATA)
+    ks = _abi.CKeySet()
+    _chk("tlsrec_tls12_make_keys", _abi.load().tlsrec_tls12_make_keys(prf, cipher, _b(master), _b(randbytes),
+                                                                      ctypes.byref(ks)))
+    return _key_set(ks)
+
+
+def tls12_export_keying_material(prf: int, master: bytes, randbytes: bytes, label: bytes, context: bytes | None,
+                                 n: int, context_len: int | None = None) -> bytes:
+    """context None = no context (use_context 0); context_len overrides
+    len(context) for the argument check of the reference."""
+    if len(master) != 48 or len(randbytes) != 64:
+        raise KeyScheduleError("tlsrec_tls12_export_keying_material", _abi.ERR_SSL_BAD_INPUT_DATA)
+    out = ctypes.create_string_buffer(max(1, n))
+    use = context is not None
+    clen = (len(context) if context_len is None else context_len) if use else 0
+    _chk("tlsrec_tls12_export_keying_material", _abi.load().tlsrec_tls12_export_keying_material(
+        prf, _b(master), _b(randbytes), bytes(label), len(label), _b(context) if use else None, clen, int(use),
+        out, n))
+    return out.raw[:n]
+
+
+def tls12_keytab_derive(kt: KeyTable, first: int, count: int, cipher: int, prf: int, conns, stream=None) -> None:
+    """`conns`: device buffer (uint8 tensor) of count x 112 bytes
+    (tlsrec_tls12_conn), only read.  Connection i's client_write key lands in
+    slot first + 2*i, its server_write key in slot first + 2*i + 1."""
+    _chk("tlsrec_tls12_keytab_derive", _abi.load().tlsrec_tls12_keytab_derive(
+        kt.handle if kt is not None else None, first, count, cipher, prf, _ptr(conns), _stream(stream)))
+
+
+def tls12_slots(first: int, i: int, endpoint: int):
+    """(enc_slot, dec_slot) of connection i for an endpoint: a server writes
+    with server_write (the odd slot) and reads with client_write; a client
+    the reverse."""
+    c, s = first + 2 * i, first + 2 * i + 1
+    return (s, c) if endpoint == IS_SERVER else (c, s)

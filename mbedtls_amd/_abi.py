@@ -229,8 +229,31 @@ def test_library():
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
+        L.tlsrec__test_launch_log_reset.restype = None
+        L.tlsrec__test_launch_log_reset.argtypes = []
+        L.tlsrec__test_launch_log_read.restype = _U32
+        L.tlsrec__test_launch_log_read.argtypes = [_VP, _U32]
         _test_lib = L
     return _test_lib
+
+
+# the launch log of the test-hooks build (csrc/tlsrec_internal.h TLSREC_LAUNCH_LOG)
+LOG_GCM, LOG_CHACHA, LOG_ALT_GCM, LOG_CCM, LOG_BUCKET, LOG_SEND_FRAME, LOG_DTLS_RX_FRAME, LOG_STREAM_RX_FRAME = \
+    1, 2, 3, 4, 5, 6, 7, 8
+LAUNCH_LOG_ENTRY = np.dtype([("kind", "<i4"), ("p0", "<i4"), ("p1", "<i4"), ("p2", "<i4"), ("p3", "<i4")])
+
+
+def launch_log_reset():
+    """Forget the test library's launch log."""
+    test_library().tlsrec__test_launch_log_reset()
+
+
+def launch_log_read(cap=256):
+    """The test library's last (up to cap) dispatch decisions, oldest first,
+    as (kind, p0, p1, p2, p3) tuples of ints."""
+    buf = np.zeros(cap, dtype=LAUNCH_LOG_ENTRY)
+    n = test_library().tlsrec__test_launch_log_read(buf.ctypes.data, cap)
+    return [tuple(int(x) for x in buf[i]) for i in range(n)]
 
 
 class use_library:

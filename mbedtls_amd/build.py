@@ -8,8 +8,8 @@ that it travels with a gpurun snapshot; objects go to build/.
 
 Beside it, libtlsrec_test.so: the same library compiled with
 -DTLSREC_TEST_HOOKS (the reference's MBEDTLS_TEST_HOOKS, ssl_misc.h:2685) --
-the tlsrec__test_* entry points and the kernels' unreached-record compare
-exist only there.  Only tests/ load it (tests/test_fail_closed_gpu.py through
+the tlsrec__test_* entry points (the dispatchers' launch log among them) and
+the kernels' unreached-record compare exist only there.  Only tests/ load it (tests/test_fail_closed_gpu.py through
 mbedtls_amd._abi.use_library); units that hold no hook share their objects.
 """
 from __future__ import annotations
@@ -40,8 +40,9 @@ UNITS = [("gcm_dec.hip", "hip"), ("gcm_enc.hip", "hip"), ("gcm_alt_dec.hip", "hi
          ("kernels.hip", "hip"), ("engine.hip", "hip"), ("keysched.hip", "hip"), ("stream.hip", "hip"), ("ccm.hip", "hip"), ("ticket.hip", "hip"),
          ("server.hip", "hip"), ("tlsrec_host.c", "c")]
 # units whose code changes under TLSREC_TEST_HOOKS (TLSREC_HOOK_SKIP, the hook entry points)
+# (stream.hip: only its host-side dispatchers, which append to the launch log)
 HOOK_UNITS = {"gcm_dec.hip", "gcm_enc.hip", "gcm_alt_dec.hip", "gcm_alt_enc.hip", "kernels.hip", "engine.hip",
-              "ccm.hip", "server.hip"}
+              "ccm.hip", "server.hip", "stream.hip"}
 
 
 def _mtime(p):

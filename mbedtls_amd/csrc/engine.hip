@@ -631,6 +631,44 @@ extern "C" void tlsrec__test_server_shadow(void *dev, size_t bytes)
     g_test_shadow = (uint8_t *) dev;
     g_test_shadow_bytes = dev ? bytes : 0;
 }
+
+/*   tlsrec__test_launch_log_*  the dispatchers' choices (tlsrec_internal.h
+ *                              TLSREC_LAUNCH_LOG): the last LAUNCH_LOG_CAP
+ *                              entries, oldest first */
+#define LAUNCH_LOG_CAP 256
+static pthread_mutex_t g_launch_log_mu = PTHREAD_MUTEX_INITIALIZER;
+static int32_t g_launch_log[LAUNCH_LOG_CAP][5];
+static uint64_t g_launch_log_n = 0;      /* entries appended since the reset */
+
+extern "C" void tlsrec__test_launch_log_add(int32_t kind, int32_t p0, int32_t p1, int32_t p2, int32_t p3)
+{
+    pthread_mutex_lock(&g_launch_log_mu);
+    int32_t *e = g_launch_log[g_launch_log_n++ % LAUNCH_LOG_CAP];
+    e[0] = kind;
+    e[1] = p0;
+    e[2] = p1;
+    e[3] = p2;
+    e[4] = p3;
+    pthread_mutex_unlock(&g_launch_log_mu);
+}
+extern "C" void tlsrec__test_launch_log_reset(void)
+{
+    pthread_mutex_lock(&g_launch_log_mu);
+    g_launch_log_n = 0;
+    pthread_mutex_unlock(&g_launch_log_mu);
+}
+/* the last min(appended, LAUNCH_LOG_CAP, cap) entries, oldest first, as 5 x
+ * int32 each; returns how many were written */
+extern "C" uint32_t tlsrec__test_launch_log_read(int32_t *entries, uint32_t cap)
+{
+    pthread_mutex_lock(&g_launch_log_mu);
+    uint64_t have = g_launch_log_n < LAUNCH_LOG_CAP ? g_launch_log_n : LAUNCH_LOG_CAP;
+    if (have > cap) have = cap;
+    for (uint64_t k = 0; k < have; k++)
+        memcpy(entries + 5 * k, g_launch_log[(g_launch_log_n - have + k) % LAUNCH_LOG_CAP], sizeof(g_launch_log[0]));
+    pthread_mutex_unlock(&g_launch_log_mu);
+    return (uint32_t) have;
+}
 #else
 static constexpr uint32_t g_test_skip = 0xffffffffu;
 #endif
@@ -704,6 +742,7 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
     const bool identity = kt->nloaded == 1 || n == 1 || opt.coalesced || grouped ||
                           kt->cipher_mask == (1u << TLSREC_CIPHER_CHACHA20_POLY1305);
     const bool keyrun = !identity || grouped;     /* the many-keys launch shapes apply */
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_BUCKET, !identity, 0, 0, 0);
     if (identity) {
         if (!prefilled && tlsrec__launch_res_guard(res, n, st) != hipSuccess) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     } else {
@@ -842,6 +881,8 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
         a.skip = skip;
         uint64_t per_wg = (uint64_t) waves * a.rpw;
         uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_GCM, L, pair ? -32 : (wp ? -8 : (kt->has_cid ? -16 : waves)), a.tm,
+                          a.src_off != nullptr);
         if (tlsrec__launch_gcm(&a, dec, L, nr, pair ? -32 : (wp ? -8 : (kt->has_cid ? -16 : waves)), grid, st) !=
             hipSuccess)
             rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
@@ -877,6 +918,7 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
         a.skip = skip;
         const uint64_t per_wg = (uint64_t) ARIA_GCM_WAVES * a.rpw;
         const uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_ALT_GCM, c, 0, 0, 0);
         if (tlsrec__launch_gcm_aria(&a, dec, (int) tlsrec_cipher_alt_nr(c), (int) kt->has_cid, grid, st) != hipSuccess)
             rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
@@ -900,6 +942,7 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
         a.flag_nr = 0;
         a.cid = kt->has_cid;
         a.skip = skip;
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_CCM, ccm_nr, 0, 0, 0);
         if (tlsrec__launch_ccm(&a, dec, ccm_nr, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     if (!rc && (cmask & (1u << TLSREC_CIPHER_CHACHA20_POLY1305))) {
@@ -926,6 +969,7 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
         a.src_off = dec ? nullptr : opt.src_off;
         uint64_t per_wg = (uint64_t) CP_WAVES * a.rpw;
         uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_CHACHA, L, a.src_off != nullptr, 0, 0);
         if (tlsrec__launch_chachapoly(&a, dec, L, grid, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     tlsrec__scratch_release(&bs.lease);

@@ -1878,6 +1878,7 @@ extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_strea
     int r = scratch_alloc(sc, nstreams, st, fused ? tiles : 0u);
     uint32_t total = 0, avg = 0;
     const bool gw = groupwalk_env();
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_STREAM_RX_FRAME, fused, gw ? frg : 1, 0, 0);
     if (r == 0 && fused) {
         /* count, scan and emit in one pass (descriptors up to max_records) */
         /* tiles of 128 connections: one chunk of 128 at 4 lanes (512 threads),
@@ -1993,6 +1994,7 @@ extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_strea
         if (tlsrec__keytab_src_ok(kt) && src_env() &&
             tlsrec__scratch_acquire(st, 3, (size_t) total * sizeof(uint64_t), &sl) == 0)
             srcoff = (uint64_t *) sl.mem;
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_SEND_FRAME, srcoff != nullptr, 0, 0, 0);
         if (srcoff) {
             hipLaunchKernelGGL(out_frame_conn_kernel<false>, dim3(blocks(nstreams, RX_CONNS)), dim3(RX_THREADS), 0, st,
                                streams, nstreams, sc.offs, sc.counts, slots, cap, in_arena, out_arena, recs, srcoff);
@@ -2063,9 +2065,10 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
          * 24 / 96 KiB per workgroup); TLSREC_DTLS_STASH=0: the emit walks the
          * headers again */
         const uint32_t per = nconns ? (uint32_t) ((ndgrams + nconns - 1) / nconns) : 0;
-#define TLSREC_DTLS_FRAME(S_) hipLaunchKernelGGL(dtls_frame_kernel<S_>, dim3(tiles), dim3(DG_THREADS), 0, st, conns, \
+#define TLSREC_DTLS_FRAME(S_) do { TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, S_, 0, 0, 0); \
+                           hipLaunchKernelGGL(dtls_frame_kernel<S_>, dim3(tiles), dim3(DG_THREADS), 0, st, conns, \
                            nconns, dgrams, ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.bytes, \
-                           sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst)
+                           sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst); } while (0)
         if (!dtls_stash_env() || per > 16) TLSREC_DTLS_FRAME(0);
         else if (per > 4) TLSREC_DTLS_FRAME(16);
         else TLSREC_DTLS_FRAME(4);
@@ -2074,6 +2077,7 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
         else if (mb) r = collect_totals(sc, nconns, st, seq, &total, &avg);
         else r = fetch_total(sc, nconns, st, &total, &avg);
     } else if (r == 0) {
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, -1, 0, 0, 0);
         hipLaunchKernelGGL(dtls_count_kernel, dim3(blocks(nconns + 1, 256)), dim3(256), 0, st, conns, nconns, dgrams,
                            ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.bytes);
         uint64_t seq = 0;
@@ -2153,6 +2157,7 @@ extern "C" int tlsrec_dtls_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_
         if (tlsrec__keytab_src_ok(kt) && src_env() &&
             tlsrec__scratch_acquire(st, 3, (size_t) total * sizeof(uint64_t), &sl) == 0)
             srcoff = (uint64_t *) sl.mem;
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_SEND_FRAME, srcoff != nullptr, 1, 0, 0);
         if (srcoff) {
             hipLaunchKernelGGL(out_frame_conn_kernel<true>, dim3(blocks(nstreams, RX_CONNS)), dim3(RX_THREADS), 0, st,
                                streams, nstreams, sc.offs, sc.counts, slots, cap, in_arena, out_arena, recs, srcoff);

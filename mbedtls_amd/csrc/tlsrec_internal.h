@@ -211,4 +211,39 @@ hipError_t tlsrec__exclusive_scan(const uint32_t *in, uint32_t *out, uint32_t n,
 hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream_t st);
 }
 
+/* Launch log (test hooks): the host-side dispatchers of engine.hip and
+ * stream.hip note which kernel shape they chose, one fixed-size entry
+ * {kind, p0, p1, p2, p3} per dispatch, so a test can assert the path its
+ * shape was built for (tlsrec__test_launch_log_reset / _read, engine.hip).
+ * In the release library the macro expands to nothing.
+ *   GCM             p0 lanes per record, p1 waves code (-32 paired wave passes,
+ *                   -8 wave passes, -16 the CID variant, else waves per
+ *                   workgroup), p2 GcmArgs::tm, p3 src_off set
+ *   CHACHA          p0 lanes per record, p1 src_off set
+ *   ALT_GCM / CCM   p0 the cipher / the nr mask
+ *   BUCKET          p0 1 = bucket pass taken, 0 = identity order
+ *   SEND_FRAME      p0 1 = out_frame_conn_kernel (contents read in place),
+ *                   0 = map + out_frame_kernel<64> (copied); p1 1 = DTLS
+ *   DTLS_RX_FRAME   p0 the stash depth S of dtls_frame_kernel (4 / 16 / 0),
+ *                   -1 = count, scan and emit kernels
+ *   STREAM_RX_FRAME p0 1 = one pass, 0 = three kernels; p1 lanes per
+ *                   connection G (1 = the one-lane walks) */
+enum {
+    TLSREC_LOG_GCM = 1,
+    TLSREC_LOG_CHACHA = 2,
+    TLSREC_LOG_ALT_GCM = 3,
+    TLSREC_LOG_CCM = 4,
+    TLSREC_LOG_BUCKET = 5,
+    TLSREC_LOG_SEND_FRAME = 6,
+    TLSREC_LOG_DTLS_RX_FRAME = 7,
+    TLSREC_LOG_STREAM_RX_FRAME = 8
+};
+#ifdef TLSREC_TEST_HOOKS
+extern "C" void tlsrec__test_launch_log_add(int32_t kind, int32_t p0, int32_t p1, int32_t p2, int32_t p3);
+#define TLSREC_LAUNCH_LOG(kind, p0, p1, p2, p3) \
+    tlsrec__test_launch_log_add((kind), (int32_t) (p0), (int32_t) (p1), (int32_t) (p2), (int32_t) (p3))
+#else
+#define TLSREC_LAUNCH_LOG(kind, p0, p1, p2, p3) ((void) 0)
+#endif
+
 #endif

@@ -46,10 +46,31 @@ def test_test_hooks_only_in_the_test_build():
     tst = _exports(_abi.TEST_LIB_PATH)
     assert not [s for s in rel if s.startswith("tlsrec__test_")], sorted(s for s in rel if "test" in s)
     for s in ("tlsrec__test_skip_record", "tlsrec__test_fail_staging", "tlsrec__test_server_shadow",
-              "tlsrec__test_lane_ops", "tlsrec__test_scan"):
+              "tlsrec__test_lane_ops", "tlsrec__test_scan", "tlsrec__test_launch_log_reset",
+              "tlsrec__test_launch_log_read"):
         assert s in tst, s
     for n in _declared():
         assert n in tst, n
+
+
+def test_launch_log_keeps_the_last_entries_in_order():
+    """The test build's launch log (host code only): reset, append, read back
+    oldest first; past its capacity the oldest entries go."""
+    L = _abi.test_library()
+    add = L.tlsrec__test_launch_log_add
+    add.restype, add.argtypes = None, [ctypes.c_int32] * 5
+    _abi.launch_log_reset()
+    assert _abi.launch_log_read() == []
+    for i in range(5):
+        add(_abi.LOG_GCM, i, -32, 9, 1)
+    assert _abi.launch_log_read() == [(_abi.LOG_GCM, i, -32, 9, 1) for i in range(5)]
+    assert _abi.launch_log_read(2) == [(_abi.LOG_GCM, i, -32, 9, 1) for i in (3, 4)]
+    for i in range(5, 1000):
+        add(_abi.LOG_CHACHA, i, -1, 0, 0)
+    got = _abi.launch_log_read(4096)
+    assert len(got) >= 64 and got == [(_abi.LOG_CHACHA, i, -1, 0, 0) for i in range(1000 - len(got), 1000)]
+    _abi.launch_log_reset()
+    assert _abi.launch_log_read() == []
 
 
 def test_struct_layouts():

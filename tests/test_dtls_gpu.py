@@ -20,6 +20,7 @@ import mbedtls_amd as M  # noqa: E402
 from mbedtls_amd import dtls as D  # noqa: E402
 from mbedtls_amd import stream as S  # noqa: E402
 import oracle as O  # noqa: E402
+from tests import batchlib as B  # noqa: E402
 from tests.prng import prng_bytes  # noqa: E402
 
 REPLAY = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "dtls_replay.json")))["cases"]
@@ -36,127 +37,7 @@ def ctr(epoch, seq):
     return epoch.to_bytes(2, "big") + (seq % (1 << 48)).to_bytes(6, "big")
 
 
-class Table:
-    """slots: list of (cipher, key, iv, cid) -- TLS 1.2 keys; a slot with a CID
-    is one direction (its out_cid when sending, in_cid when receiving)."""
-
-    def __init__(self, slots, tls=M.VERSION_TLS1_2):
-        self.slots = slots
-        self.kt = M.KeyTable(len(slots))
-        self.kt.load(np.concatenate([M.key_material(c, tls, k, iv) for c, k, iv, _ in slots]))
-        self.ot = []
-        for s, (c, k, iv, cid) in enumerate(slots):
-            if cid:
-                self.kt.set_cid(s, cid)
-            t = O.Transform(O.TLS1_2 if tls == M.VERSION_TLS1_2 else O.TLS1_3, c, k, k, iv, iv)
-            t.set_cid(cid, cid)
-            self.ot.append(t)
-        torch.cuda.synchronize()
-
-    def encrypt(self, jobs):
-        """jobs: (slot, plaintext, out_ctr bytes, max_frag, type) -> [(res, datagram bytes back to back, recs, res)]"""
-        d = np.zeros(len(jobs), dtype=S.STREAM_OUT)
-        pos_in, pos_out, outs, ins = 0, 0, [], []
-        for i, (slot, pt, c8, frag, typ) in enumerate(jobs):
-            c, _, _, cid = self.slots[slot]
-            size = D.out_size(c, 0, len(cid), len(pt), frag)
-            d[i]["in_off"], d[i]["in_len"], d[i]["slot"] = pos_in, len(pt), slot
-            d[i]["out_off"], d[i]["max_frag"], d[i]["type"] = pos_out, frag, typ
-            d[i]["out_ctr"] = np.frombuffer(c8, dtype=np.uint8)
-            ins.append(pos_in)
-            outs.append((pos_out, size))
-            pos_in += _al(len(pt) + 1)
-            pos_out += _al(size + 1)
-        ina = np.zeros(max(pos_in, 16), dtype=np.uint8)
-        for (slot, pt, *_), o in zip(jobs, ins):
-            ina[o:o + len(pt)] = np.frombuffer(pt, dtype=np.uint8)
-        tin = torch.from_numpy(ina).to(DEV)
-        tout = torch.zeros(max(pos_out, 16), dtype=torch.uint8, device=DEV)
-        nmax = sum((len(j[1]) + (j[3] or 16384) - 1) // (j[3] or 16384) for j in jobs) + 1
-        recs = torch.zeros(nmax * 40, dtype=torch.uint8, device=DEV)
-        res = torch.zeros(nmax * 16, dtype=torch.uint8, device=DEV)
-        sres = torch.zeros(len(jobs) * 32, dtype=torch.uint8, device=DEV)
-        D.encrypt(self.kt, d, len(jobs), tin, tout, recs, res, nmax, sres)
-        torch.cuda.synchronize()
-        o = tout.cpu().numpy()
-        sr = sres.cpu().numpy().view(S.STREAM_OUT_RES)
-        rc = recs.cpu().numpy().view(M.BATCH_REC)
-        rs = res.cpu().numpy().view(M.BATCH_RES)
-        self.last_regions = [o[p:p + size].tobytes() for p, size in outs]   # each job's whole output region
-        return [(sr[i], o[p:p + int(sr[i]["out_len"])].tobytes(), rc, rs) for i, (p, _) in enumerate(outs)]
-
-    def decrypt(self, conns):
-        """conns: (slot, dict of DtlsState fields, [datagram bytes])"""
-        d = np.zeros(len(conns), dtype=D.DTLS_IN)
-        dgl, pos, offs = [], 0, []
-        for i, (slot, stt, dgs) in enumerate(conns):
-            d[i]["first_dgram"], d[i]["ndgram"], d[i]["slot"] = len(dgl), len(dgs), slot
-            d[i]["window_top"], d[i]["window"] = stt.get("window_top", 0), stt.get("window", 0)
-            d[i]["badmac_seen"], d[i]["badmac_limit"] = stt.get("badmac_seen", 0), stt.get("badmac_limit", 0)
-            d[i]["in_epoch"], d[i]["cid_len"], d[i]["nb_zero"] = stt.get("in_epoch", 0), stt.get("cid_len", 0), \
-                stt.get("nb_zero", 0)
-            d[i]["flags"] = (M.DTLS_ANTI_REPLAY if stt.get("anti_replay", 1) else 0) | \
-                (M.DTLS_IGNORE_UNEXPECTED_CID if stt.get("ignore_unexpected_cid", 0) else 0)
-            o = []
-            for g in dgs:
-                dgl.append((pos, len(g)))
-                o.append(pos)
-                pos += _al(len(g) + 3) + 16 * (len(dgl) % 3)     # assorted alignments
-            offs.append(o)
-        a = np.zeros(max(pos, 16), dtype=np.uint8)
-        for (slot, stt, dgs), o in zip(conns, offs):
-            for g, p in zip(dgs, o):
-                a[p:p + len(g)] = np.frombuffer(g, dtype=np.uint8)
-        dg = np.zeros(max(1, len(dgl)), dtype=D.DGRAM)
-        for k, (p, L) in enumerate(dgl):
-            dg[k]["off"], dg[k]["len"] = p, L
-        ta = torch.from_numpy(a).to(DEV)
-        nmax = sum(len(g) // 13 + 1 for c in conns for g in c[2]) + 1
-        recs = torch.zeros(nmax * 40, dtype=torch.uint8, device=DEV)
-        res = torch.zeros(nmax * 16, dtype=torch.uint8, device=DEV)
-        disp = torch.zeros(nmax, dtype=torch.int32, device=DEV)
-        cres = torch.zeros(len(conns) * 48, dtype=torch.uint8, device=DEV)
-        D.decrypt(self.kt, d, len(conns), dg, len(dgl), ta, recs, res, disp, nmax, cres)
-        torch.cuda.synchronize()
-        return (ta.cpu().numpy(), recs.cpu().numpy().view(M.BATCH_REC), res.cpu().numpy().view(M.BATCH_RES),
-                disp.cpu().numpy(), cres.cpu().numpy().view(D.DTLS_IN_RES), offs)
-
-    def close(self):
-        self.kt.close()
-
-
-def check_vs_oracle(tab, conns, got):
-    a, recs, res, disp, cres, offs = got
-    for i, (slot, stt, dgs) in enumerate(conns):
-        st = O.DtlsState()
-        st.anti_replay = stt.get("anti_replay", 1)
-        for f in ("window_top", "window", "badmac_seen", "badmac_limit", "in_epoch", "cid_len",
-                  "ignore_unexpected_cid", "nb_zero"):
-            if f in stt:
-                setattr(st, f, stt[f])
-        want, wrecs, after = O.dtls_decrypt(tab.ot[slot], st, dgs)
-        g = cres[i]
-        assert (int(g["status"]), int(g["nrec"]), int(g["naccepted"]), int(g["dgrams_done"]),
-                int(g["invalid_dgrams"])) == (want["status"], want["nrec"], want["naccepted"],
-                                              want["dgrams_done"], want["invalid_dgrams"]), (i, want)
-        assert (int(g["window_top"]), int(g["window"]), int(g["badmac_seen"]), int(g["nb_zero"])) == \
-            (st.window_top, st.window, st.badmac_seen, st.nb_zero), i
-        f = int(g["first"])
-        for k, (dgi, off, doff, dlen, dsp, typ) in enumerate(wrecs):
-            assert int(disp[f + k]) == dsp, (i, k, dsp, int(disp[f + k]))
-            assert int(recs[f + k]["buf_off"]) == offs[i][dgi] + off, (i, k)
-            if dsp in (M.DTLS_DROPPED, M.DTLS_NOT_REACHED, M.ERR_SSL_UNEXPECTED_RECORD):
-                # never decrypted by the reference: no plaintext may be left
-                # (each byte is the received one, or wiped to zero)
-                s0 = offs[i][dgi] + off
-                got_b = a[s0:s0 + doff + dlen]
-                rx = np.frombuffer(after[dgi][off:off + doff + dlen], dtype=np.uint8)
-                assert ((got_b == rx) | (got_b == 0)).all(), (i, k, dsp)
-            if dsp == 0:
-                r = res[f + k]
-                assert (int(r["data_offset"]), int(r["data_len"]), int(r["type"])) == (doff, dlen, typ), (i, k)
-                s0 = offs[i][dgi] + off + doff
-                assert a[s0:s0 + dlen].tobytes() == after[dgi][off + doff:off + doff + dlen], (i, k)
+Table, check_vs_oracle = B.Table, B.check_vs_oracle      # (the harness lives in tests/batchlib.py)
 
 
 def _slots(seed, cid_every=0):

@@ -26,75 +26,7 @@ OC = {c: c for c in M.KEYLEN}      # the oracle uses the same cipher ids as incl
 assert O.AES_256_CCM_8 == M.CIPHER_AES_256_CCM_8 and O.CHACHA20_POLY1305 == M.CIPHER_CHACHA20_POLY1305
 
 
-def _al(x, a=128):
-    return (x + a - 1) // a * a
-
-
-class Conns:
-    """slots: list of (cipher, version, key, iv, granularity); one key table."""
-
-    def __init__(self, slots):
-        self.slots = slots
-        self.kt = M.KeyTable(len(slots))
-        self.kt.load(np.concatenate([M.key_material(c, v, k, iv, g) for c, v, k, iv, g in slots]))
-        self.ot = [O.Transform(v, OC[c], k, k, iv, iv, granularity=g or 16) for c, v, k, iv, g in slots]
-
-    def encrypt(self, jobs):
-        """jobs: list of (slot, plaintext, out_ctr(int), max_frag, type)"""
-        ins, outs, pos_in, pos_out = [], [], 0, 0
-        d = np.zeros(len(jobs), dtype=S.STREAM_OUT)
-        for i, (slot, pt, ctr, frag, typ) in enumerate(jobs):
-            c, v, _, _, g = self.slots[slot]
-            size = S.out_size(v, c, g, len(pt), frag)
-            d[i]["in_off"], d[i]["in_len"], d[i]["slot"] = pos_in, len(pt), slot
-            d[i]["out_off"], d[i]["max_frag"], d[i]["type"] = pos_out, frag, typ
-            d[i]["out_ctr"] = np.frombuffer(ctr.to_bytes(8, "big"), dtype=np.uint8)
-            ins.append(pos_in)
-            outs.append((pos_out, size))
-            pos_in += _al(len(pt) + 1)
-            pos_out += _al(size + 1)
-        ina = np.zeros(max(pos_in, 16), dtype=np.uint8)
-        for (slot, pt, *_), o in zip(jobs, ins):
-            ina[o:o + len(pt)] = np.frombuffer(pt, dtype=np.uint8)
-        dev = torch.device("cuda")
-        tin = torch.from_numpy(ina).to(dev)
-        tout = torch.zeros(max(pos_out, 16), dtype=torch.uint8, device=dev)
-        nmax = sum((len(j[1]) + (j[3] or 16384) - 1) // (j[3] or 16384) for j in jobs) + 1
-        recs = torch.zeros(nmax * 40, dtype=torch.uint8, device=dev)
-        res = torch.zeros(nmax * 16, dtype=torch.uint8, device=dev)
-        sres = torch.zeros(len(jobs) * 32, dtype=torch.uint8, device=dev)
-        S.encrypt(self.kt, d, len(jobs), tin, tout, recs, res, nmax, sres)
-        torch.cuda.synchronize()
-        o = tout.cpu().numpy()
-        sr = sres.cpu().numpy().view(S.STREAM_OUT_RES)
-        self.last_regions = [o[p:p + size].tobytes() for p, size in outs]   # each job's whole output region
-        return [(sr[i], o[p:p + int(sr[i]["out_len"])].tobytes()) for i, (p, _) in enumerate(outs)]
-
-    def decrypt(self, conns):
-        """conns: list of (slot, bytes, in_ctr(int), nb_zero)"""
-        d = np.zeros(len(conns), dtype=S.STREAM_IN)
-        pos, offs = 0, []
-        for i, (slot, data, ctr, nbz) in enumerate(conns):
-            d[i]["off"], d[i]["len"], d[i]["slot"], d[i]["nb_zero"] = pos, len(data), slot, nbz
-            d[i]["in_ctr"] = np.frombuffer(ctr.to_bytes(8, "big"), dtype=np.uint8)
-            offs.append(pos)
-            pos += _al(len(data) + 1)
-        a = np.zeros(max(pos, 16), dtype=np.uint8)
-        for (slot, data, *_), o in zip(conns, offs):
-            a[o:o + len(data)] = np.frombuffer(data, dtype=np.uint8)
-        dev = torch.device("cuda")
-        ta = torch.from_numpy(a).to(dev)
-        nmax = sum(len(c[1]) // 6 + 1 for c in conns)
-        recs = torch.zeros(nmax * 40, dtype=torch.uint8, device=dev)
-        res = torch.zeros(nmax * 16, dtype=torch.uint8, device=dev)
-        sres = torch.zeros(len(conns) * 32, dtype=torch.uint8, device=dev)
-        S.decrypt(self.kt, d, len(conns), ta, recs, res, nmax, sres)
-        torch.cuda.synchronize()
-        return (ta.cpu().numpy(), recs.cpu().numpy().view(M.BATCH_REC), res.cpu().numpy().view(M.BATCH_RES),
-                sres.cpu().numpy().view(S.STREAM_IN_RES), offs)
-
-    def close(self):
-        self.kt.close()
+Conns = B.Conns      # (the harness lives in tests/batchlib.py, shared with test_send_inplace_gpu.py)
 
 
 @pytest.mark.parametrize("kat", KATS, ids=lambda k: k["name"])

@@ -28,6 +28,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "tlsrec.h"
 #include "tlsrec_frame.h"
 #include "tlsrec_internal.h"
@@ -153,6 +155,25 @@ __global__ void in_count_kernel(const tlsrec_stream_in *s, uint32_t n, const uin
     wave_add_bytes(bytes, b);
 }
 
+/* the descriptor of the record whose header (type, v0 v1, dlen) is at pos,
+ * with sequence number seq */
+__device__ __forceinline__ tlsrec_batch_rec rx_desc(const tlsrec_stream_in &si, bool tls13, uint32_t pos, uint32_t type,
+                                                    uint8_t v0, uint8_t v1, uint32_t dlen, uint64_t seq)
+{
+    tlsrec_batch_rec d;
+    memset(&d, 0, sizeof(d));
+    d.buf_off = si.off + pos;                               /* rec->buf = header (:3715-3716) */
+    d.buf_len = 5 + dlen;
+    d.data_offset = 5;
+    d.data_len = dlen;
+    d.slot = (tls13 && type == 20) ? NO_SLOT : si.slot;     /* TLS 1.3 CCS: not decrypted, no in_ctr step */
+    put_be64(d.ctr, seq);
+    d.type = (uint8_t) type;
+    d.ver[0] = v0;
+    d.ver[1] = v1;
+    return d;
+}
+
 __global__ void in_emit_kernel(const tlsrec_stream_in *s, uint32_t n, const uint8_t *arena, const uint32_t *offs,
                                const SlotState *slots, uint32_t cap, tlsrec_batch_rec *recs, uint32_t max_records,
                                tlsrec_batch_res *res)
@@ -164,19 +185,8 @@ __global__ void in_emit_kernel(const tlsrec_stream_in *s, uint32_t n, const uint
     uint64_t seq = be64(si.in_ctr);
     tlsrec_batch_rec *out = recs + offs[i];
     walk_in(arena + si.off, si.len, [&](uint32_t k, uint32_t pos, uint32_t type, uint8_t v0, uint8_t v1, uint32_t dlen) {
-        tlsrec_batch_rec d;
-        memset(&d, 0, sizeof(d));
-        d.buf_off = si.off + pos;                 /* rec->buf = header (:3715-3716) */
-        d.buf_len = 5 + dlen;
-        d.data_offset = 5;
-        d.data_len = dlen;
-        const bool ccs = tls13 && type == 20;      /* TLS 1.3 CCS: not decrypted, no in_ctr step */
-        d.slot = ccs ? NO_SLOT : si.slot;
-        put_be64(d.ctr, seq);
-        d.type = (uint8_t) type;
-        d.ver[0] = v0;
-        d.ver[1] = v1;
-        if (!ccs) seq++;
+        const tlsrec_batch_rec d = rx_desc(si, tls13, pos, type, v0, v1, dlen, seq);
+        if (!(tls13 && type == 20)) seq++;                  /* (a TLS 1.3 CCS takes no number) */
         if (offs[i] + k < max_records) {                /* (launched before the host has checked the total) */
             out[k] = d;
             guard_result(&res[offs[i] + k]);
@@ -387,18 +397,8 @@ __global__ __launch_bounds__(RX_THREADS) void in_emit_group_kernel(const tlsrec_
     tlsrec_batch_rec *out = recs + offs[i];
     uint32_t cnt;
     group_walk<G>(arena + si.off, si.len, lane, tls13, &cnt, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
-        tlsrec_batch_rec d;
-        memset(&d, 0, sizeof(d));
-        d.buf_off = si.off + h.pos;                     /* rec->buf = header (:3715-3716) */
-        d.buf_len = 5 + h.dlen;
-        d.data_offset = 5;
-        d.data_len = h.dlen;
-        const bool ccs = tls13 && h.type == 20;         /* TLS 1.3 CCS: not decrypted, no in_ctr step */
-        d.slot = ccs ? NO_SLOT : si.slot;
-        put_be64(d.ctr, seq0 + (k - ccs_before));       /* in_ctr + the records before that took a number */
-        d.type = (uint8_t) h.type;
-        d.ver[0] = h.v0;
-        d.ver[1] = h.v1;
+        /* in_ctr + the records before that took a number */
+        const tlsrec_batch_rec d = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
         if (offs[i] + k < max_records) {                /* (launched before the host has checked the total) */
             out[k] = d;
             guard_result(&res[offs[i] + k]);
@@ -577,25 +577,13 @@ __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s,
         uint32_t c2;
         group_walk<G>(arena + si.off, si.len, lane, tls13, &c2, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
             if (off + k >= max_records) return;
-            tlsrec_batch_rec d;
-            memset(&d, 0, sizeof(d));
-            d.buf_off = si.off + h.pos;                     /* rec->buf = header (:3715-3716) */
-            d.buf_len = 5 + h.dlen;
-            d.data_offset = 5;
-            d.data_len = h.dlen;
-            const bool ccs = tls13 && h.type == 20;         /* TLS 1.3 CCS: not decrypted, no in_ctr step */
-            d.slot = ccs ? NO_SLOT : si.slot;
-            put_be64(d.ctr, seq0 + (k - ccs_before));
-            d.type = (uint8_t) h.type;
-            d.ver[0] = h.v0;
-            d.ver[1] = h.v1;
-            out[k] = d;
+            out[k] = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
             guard_result(&res[off + k]);
         });
     }
 }
 
-/* ---------------- send ------------------------------------------------- */
+/* ---------------- send (TLS streams and DTLS 1.2) ----------------------- */
 struct OutShape {
     uint32_t ok;              /* slot usable */
     uint32_t head;            /* explicit-IV room before the content (8 for TLS 1.2 GCM / CCM) */
@@ -616,26 +604,139 @@ __device__ __forceinline__ OutShape out_shape(const SlotState *slots, uint32_t c
     return o;
 }
 
-/* protected length of an n-byte record (ssl_msg.c:853-868, :1066-1075) */
-__device__ __forceinline__ uint32_t out_body(const OutShape &o, uint32_t n)
-{
-    if (o.tls13) {
-        const uint32_t inner = n + 1;
-        return inner + (o.gran - inner % o.gran) % o.gran + o.tag;
-    }
-    return o.head + n + o.tag;
-}
-
 __device__ __forceinline__ uint32_t frag_of(const tlsrec_stream_out &s) { return s.max_frag ? s.max_frag : 16384u; }
 
-__global__ void out_count_kernel(const tlsrec_stream_out *s, uint32_t n, const SlotState *slots, uint32_t cap,
-                                 uint32_t *counts, unsigned long long *bytes)
+/* n content bytes, the inner plaintext's type byte, and zeros up to a
+ * multiple of gran (ssl_build_inner_plaintext, ssl_msg.c:853-868 / :874-897) */
+template <typename T>
+__host__ __device__ inline T inner_len(T n, T gran)
+{
+    const T inner = n + 1;
+    return inner + (gran - inner % gran) % gran;
+}
+
+/* The two wire formats of the send path: what differs between a TLS stream
+ * and DTLS 1.2 datagrams, and nothing else.  Counters are the big-endian
+ * value of out_ctr; M48 masks DTLS's sequence number below its epoch.
+ * body(): the protected length of an n-byte record, from the slot on the
+ * device and from the cipher id in tlsrec_*_out_size.
+ * CHECK_RES_LEN: the one difference in the finish check.  Both sides restate
+ * what mbedtls_ssl_write_record does with mbedtls_ssl_encrypt_buf's result:
+ * the stream side only its "rec.data_offset != 0 -> INTERNAL_ERROR"
+ * (:2704-2707); the DTLS side (the encrypt_buf call, :2697-2700) also takes a
+ * rec.data_len other than body(len) as INTERNAL_ERROR.  The two were written
+ * that way and are kept so here; neither is "fixed" towards the other. */
+constexpr uint64_t M48 = 0xFFFFFFFFFFFFull;
+
+struct TlsWire {
+    static constexpr int LOG_P1 = 0;
+    static constexpr uint8_t VER0 = 3, VER1 = 3;   /* mbedtls_ssl_write_version(TLS 1.2 for 1.3), :2669-2674 */
+    static constexpr bool CHECK_RES_LEN = false;
+    static __device__ __forceinline__ bool usable(const OutShape &sh) { return sh.ok; }
+    static __device__ __forceinline__ uint32_t cid_len(const OutShape &, const SlotState *, uint32_t) { return 0; }
+    static __device__ __forceinline__ uint32_t hdr(uint32_t) { return 5; }
+    static __device__ __forceinline__ bool padded(const OutShape &sh, uint32_t) { return sh.tls13; }
+    /* (:853-868, :1066-1075: a TLS 1.3 record has no explicit IV) */
+    template <typename T>
+    static __host__ __device__ inline T body(T head, T tag, T gran, bool padded, T n)
+    {
+        return padded ? inner_len(n, gran) + tag : head + n + tag;
+    }
+    static __device__ __forceinline__ bool past_wrap(uint64_t ctr0, uint64_t k) { return k > ~ctr0; }
+    static __device__ __forceinline__ uint64_t ctr_of(uint64_t ctr0, uint64_t k) { return ctr0 + k; }
+    static __device__ __forceinline__ bool step(uint64_t &ctr) { return ++ctr == 0; }        /* :2749-2756 */
+    static __device__ __forceinline__ uint32_t buf_len(uint32_t) { return TLSREC_OUT_BUF_SPACE; }
+    static __device__ __forceinline__ void header(uint8_t *h, const tlsrec_stream_out &si, const OutShape &sh,
+                                                  const SlotState *, uint32_t, const uint8_t *, uint32_t body)
+    {
+        h[0] = sh.tls13 ? (uint8_t) TLSREC_MSG_APPLICATION_DATA : si.type;   /* final out_msgtype */
+        h[1] = VER0;
+        h[2] = VER1;
+        h[3] = (uint8_t) (body >> 8);
+        h[4] = (uint8_t) body;
+    }
+};
+
+struct DtlsWire {
+    static constexpr int LOG_P1 = 1;
+    static constexpr uint8_t VER0 = 0xfe, VER1 = 0xfd;   /* mbedtls_ssl_write_version, DTLS 1.2 */
+    static constexpr bool CHECK_RES_LEN = true;
+    static __device__ __forceinline__ bool usable(const OutShape &sh) { return sh.ok && !sh.tls13; }
+    static __device__ __forceinline__ uint32_t cid_len(const OutShape &sh, const SlotState *slots, uint32_t slot)
+    {
+        return sh.ok ? slots[slot].cid_len : 0;          /* (an unusable slot may lie outside the table) */
+    }
+    static __device__ __forceinline__ uint32_t hdr(uint32_t cid) { return 13 + cid; }
+    static __device__ __forceinline__ bool padded(const OutShape &, uint32_t cid) { return cid != 0; }
+    /* (DTLSInnerPlaintext with a CID, :874-897) */
+    template <typename T>
+    static __host__ __device__ inline T body(T head, T tag, T gran, bool padded, T n)
+    {
+        return head + (padded ? inner_len(n, gran) : n) + tag;
+    }
+    static __device__ __forceinline__ bool past_wrap(uint64_t ctr0, uint64_t k) { return k > M48 - (ctr0 & M48); }
+    static __device__ __forceinline__ uint64_t ctr_of(uint64_t ctr0, uint64_t k)
+    {
+        return (ctr0 & ~M48) | ((ctr0 + k) & M48);       /* the epoch bytes kept */
+    }
+    static __device__ __forceinline__ bool step(uint64_t &ctr)                             /* :2741-2756, ep_len = 2 */
+    {
+        ctr = ctr_of(ctr, 1);
+        return (ctr & M48) == 0;
+    }
+    static __device__ __forceinline__ uint32_t buf_len(uint32_t hdr)
+    {
+        return TLSREC_DTLS_OUT_BUFFER_LEN - hdr;         /* out_buf_len - (out_iv - out_buf) */
+    }
+    /* type after encryption, FE FD, epoch + sequence, out_cid, protected length (:2669-2727) */
+    static __device__ __forceinline__ void header(uint8_t *h, const tlsrec_stream_out &si, const OutShape &,
+                                                  const SlotState *slots, uint32_t cid, const uint8_t *ctr,
+                                                  uint32_t body)
+    {
+        h[0] = cid ? (uint8_t) TLSREC_MSG_CID : si.type;     /* the type encrypt_buf leaves (:2727) */
+        h[1] = VER0;
+        h[2] = VER1;
+        memcpy(h + 3, ctr, 8);
+        memcpy(h + 11, slots[si.slot].cid, cid);              /* out_cid (:2712-2714) */
+        h[11 + cid] = (uint8_t) (body >> 8);
+        h[12 + cid] = (uint8_t) body;
+    }
+};
+
+/* what the send kernels need of a connection, computed once per thread */
+template <typename W>
+struct SendConn {
+    uint32_t frag;            /* (first: its load is issued before out_shape's dependent ones) */
+    OutShape sh;
+    uint32_t cid, hdr;
+
+    __device__ __forceinline__ SendConn(const tlsrec_stream_out &si, const SlotState *slots, uint32_t cap)
+        : frag(frag_of(si)), sh(out_shape(slots, cap, si.slot)), cid(W::cid_len(sh, slots, si.slot)),
+          hdr(W::hdr(cid))
+    {
+    }
+    /* protected length of an n-byte record */
+    __device__ __forceinline__ uint32_t body(uint32_t n) const
+    {
+        return W::body(sh.head, sh.tag, sh.gran, W::padded(sh, cid), n);
+    }
+    /* content bytes of record k */
+    __device__ __forceinline__ uint32_t len(const tlsrec_stream_out &si, uint32_t k) const
+    {
+        const uint64_t left = (uint64_t) si.in_len - (uint64_t) k * frag;
+        return left < frag ? (uint32_t) left : frag;
+    }
+};
+
+template <typename W>
+__global__ void send_count_kernel(const tlsrec_stream_out *s, uint32_t n, const SlotState *slots, uint32_t cap,
+                                  uint32_t *counts, unsigned long long *bytes)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long b = 0;
     if (i < n) {
         const uint32_t f = frag_of(s[i]);
-        const bool ok = out_shape(slots, cap, s[i].slot).ok;
+        const bool ok = W::usable(out_shape(slots, cap, s[i].slot));
         counts[i] = ok ? (uint32_t) (((uint64_t) s[i].in_len + f - 1) / f) : 0u;
         b = ok ? s[i].in_len : 0;
     } else if (i == n) {
@@ -668,22 +769,19 @@ __global__ void __launch_bounds__(256) out_map_kernel(uint32_t n, const uint32_t
 /* record k (= j - offs[i]) of connection i: header, descriptor, and the
  * content (srcoff: its offset for the AEAD to read in place; else copied
  * into the record's slot by the LPR lanes) */
-template <int LPR>
-__device__ __forceinline__ void out_frame_one(const tlsrec_stream_out &si, uint32_t k, uint32_t j, uint32_t lane,
-                                              const SlotState *slots, uint32_t cap, const uint8_t *in, uint8_t *out,
-                                              tlsrec_batch_rec *recs, uint64_t *srcoff)
+template <typename W, int LPR>
+__device__ __forceinline__ void send_frame_one(const tlsrec_stream_out &si, const SendConn<W> &c, uint32_t k,
+                                               uint32_t j, uint32_t lane, const SlotState *slots, const uint8_t *in,
+                                               uint8_t *out, tlsrec_batch_rec *recs, uint64_t *srcoff)
 {
-    const uint32_t f = frag_of(si);
-    const OutShape sh = out_shape(slots, cap, si.slot);
-    const uint64_t src_off = (uint64_t) k * f;
-    const uint64_t left = (uint64_t) si.in_len - src_off;
-    const uint32_t len = left < f ? (uint32_t) left : f;
-    const uint64_t pos = si.out_off + (uint64_t) k * (5 + out_body(sh, f));
+    const uint64_t src_off = (uint64_t) k * c.frag;
+    const uint32_t len = c.len(si, k);
+    const uint64_t pos = si.out_off + (uint64_t) k * (c.hdr + c.body(c.frag));
     /* a record whose sequence number would come after the counter wrapped is
      * never protected: the reference stops with COUNTER_WRAPPING after the
-     * record that wraps it (:2749-2756), before encrypting anything under a
+     * record that wraps it (:2741-2756), before encrypting anything under a
      * reused sequence number (= a reused nonce).  No slot, no bytes. */
-    if ((uint64_t) k > ~be64(si.out_ctr)) {
+    if (W::past_wrap(be64(si.out_ctr), k)) {
         if (lane == 0) {
             tlsrec_batch_rec d;
             memset(&d, 0, sizeof(d));
@@ -696,7 +794,7 @@ __device__ __forceinline__ void out_frame_one(const tlsrec_stream_out &si, uint3
         if (lane == 0) srcoff[j] = si.in_off + src_off;
     } else {
         const uint8_t *src = in + si.in_off + src_off;
-        uint8_t *dst = out + pos + 5 + sh.head;
+        uint8_t *dst = out + pos + c.hdr + c.sh.head;
         const uint32_t nv = len / 16;
         for (uint32_t v = lane; v < nv; v += LPR) {
             uint4 w;
@@ -706,58 +804,79 @@ __device__ __forceinline__ void out_frame_one(const tlsrec_stream_out &si, uint3
         for (uint32_t b = nv * 16 + lane; b < len; b += LPR) dst[b] = src[b];
     }
     if (lane == 0) {
-        const uint32_t body = out_body(sh, len);
-        uint8_t *h = out + pos;
-        h[0] = sh.tls13 ? (uint8_t) TLSREC_MSG_APPLICATION_DATA : si.type;   /* final out_msgtype */
-        h[1] = 3;                                  /* mbedtls_ssl_write_version(TLS 1.2 for 1.3), :2669-2674 */
-        h[2] = 3;
-        h[3] = (uint8_t) (body >> 8);
-        h[4] = (uint8_t) body;
         tlsrec_batch_rec d;
         memset(&d, 0, sizeof(d));
-        d.buf_off = pos + 5;                       /* rec.buf = out_iv */
-        d.buf_len = TLSREC_OUT_BUF_SPACE;
-        d.data_offset = sh.head;                   /* out_msg - out_iv */
+        put_be64(d.ctr, W::ctr_of(be64(si.out_ctr), k));
+        W::header(out + pos, si, c.sh, slots, c.cid, d.ctr, c.body(len));
+        d.buf_off = pos + c.hdr;                   /* rec.buf = out_iv */
+        d.buf_len = W::buf_len(c.hdr);
+        d.data_offset = c.sh.head;                 /* out_msg - out_iv */
         d.data_len = len;
         d.slot = si.slot;
-        put_be64(d.ctr, be64(si.out_ctr) + k);
         d.type = si.type;
-        d.ver[0] = 3;
-        d.ver[1] = 3;
+        d.ver[0] = W::VER0;
+        d.ver[1] = W::VER1;
         recs[j] = d;
     }
 }
 
-template <int LPR>
-__global__ void __launch_bounds__(256) out_frame_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs,
-                                                        uint32_t total, const SlotState *slots, uint32_t cap,
-                                                        const uint8_t *in, uint8_t *out, tlsrec_batch_rec *recs,
-                                                        uint64_t *srcoff)
+/* the copy path, after out_map_kernel */
+template <typename W, int LPR>
+__global__ void __launch_bounds__(256) send_frame_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs,
+                                                         uint32_t total, const SlotState *slots, uint32_t cap,
+                                                         const uint8_t *in, uint8_t *out, tlsrec_batch_rec *recs,
+                                                         uint64_t *srcoff)
 {
     const uint32_t j = blockIdx.x * (256 / LPR) + threadIdx.x / LPR, lane = threadIdx.x % LPR;
     if (j >= total) return;
     const uint32_t i = recs[j].slot;              /* connection of record j (out_map_kernel) */
-    out_frame_one<LPR>(s[i], j - offs[i], j, lane, slots, cap, in, out, recs, srcoff);
+    const uint32_t k = j - offs[i];
+    send_frame_one<W, LPR>(s[i], SendConn<W>(s[i], slots, cap), k, j, lane, slots, in, out, recs, srcoff);
 }
 
-__global__ void out_finish_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs, const uint32_t *counts,
-                                  const SlotState *slots, uint32_t cap, const tlsrec_batch_res *res,
-                                  tlsrec_stream_out_res *sres)
+/* (r06) The in-place send frame (srcoff) with a group of RG lanes per
+ * connection: lane q frames records q, q + RG, ... of its connection, so no
+ * out_map pass has to tell each record its connection (a 4-byte write into
+ * every descriptor, 17-37 us of a 1 M-record send) and a connection's
+ * descriptor and slot are read once per group, not once per record. */
+template <typename W>
+__global__ void __launch_bounds__(RX_THREADS) out_frame_conn_kernel(const tlsrec_stream_out *s, uint32_t n,
+                                                                    const uint32_t *offs, const uint32_t *counts,
+                                                                    const SlotState *slots, uint32_t cap,
+                                                                    const uint8_t *in, uint8_t *out,
+                                                                    tlsrec_batch_rec *recs, uint64_t *srcoff)
+{
+    const uint32_t i = blockIdx.x * RX_CONNS + threadIdx.x / RG, q = threadIdx.x % RG;
+    if (i >= n) return;
+    const tlsrec_stream_out si = s[i];
+    const uint32_t first = offs[i], cnt = counts[i];
+    const SendConn<W> c(si, slots, cap);
+    for (uint32_t k = q; k < cnt; k += RG) send_frame_one<W, 1>(si, c, k, first + k, 0, slots, in, out, recs, srcoff);
+}
+
+template <typename W>
+__global__ void send_finish_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs,
+                                   const uint32_t *counts, const SlotState *slots, uint32_t cap,
+                                   const tlsrec_batch_res *res, tlsrec_stream_out_res *sres)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const tlsrec_stream_out si = s[i];
+    const SendConn<W> c(si, slots, cap);
     uint64_t ctr = be64(si.out_ctr);
-    int32_t st = out_shape(slots, cap, si.slot).ok || si.in_len == 0 ? 0 : TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    int32_t st = W::usable(c.sh) || si.in_len == 0 ? 0 : TLSREC_ERR_SSL_BAD_INPUT_DATA;
     uint32_t nrec = 0, olen = 0;
     const uint32_t first = offs[i], cnt = counts[i];
     for (uint32_t k = 0; k < cnt && st == 0; k++) {
         const tlsrec_batch_res &r = res[first + k];
         if (r.status) { st = r.status; break; }
-        if (r.data_offset != 0) { st = TLSREC_ERR_SSL_INTERNAL_ERROR; break; }   /* :2704-2707 */
-        olen += 5 + r.data_len;
+        if (r.data_offset != 0 || (W::CHECK_RES_LEN && r.data_len != c.body(c.len(si, k)))) {   /* see the wire types */
+            st = TLSREC_ERR_SSL_INTERNAL_ERROR;
+            break;
+        }
+        olen += c.hdr + r.data_len;
         nrec++;
-        if (++ctr == 0) st = TLSREC_ERR_SSL_COUNTER_WRAPPING;                      /* :2749-2756 */
+        if (W::step(ctr)) st = TLSREC_ERR_SSL_COUNTER_WRAPPING;
     }
     tlsrec_stream_out_res o;
     memset(&o, 0, sizeof(o));
@@ -1416,188 +1535,6 @@ __global__ void dtls_finish_kernel(const tlsrec_dtls_in *c, uint32_t n, const tl
     if (i < n) dtls_finish_one<PRE>(i, c, dg, ndg, arena, offs, counts, slots, cap, recs, res, disp, cres, dgst);
 }
 
-/* send: one record per datagram */
-__device__ __forceinline__ uint32_t dtls_cid_of(const SlotState *slots, uint32_t slot) { return slots[slot].cid_len; }
-
-/* protected length of an n-byte record under a TLS 1.2 key (DTLSInnerPlaintext with a CID, :874-897) */
-__device__ __forceinline__ uint32_t dtls_body(const OutShape &o, uint32_t cid, uint32_t n)
-{
-    if (cid) {
-        const uint32_t inner = n + 1;
-        return o.head + inner + (o.gran - inner % o.gran) % o.gran + o.tag;
-    }
-    return o.head + n + o.tag;
-}
-
-__global__ void dtls_out_count_kernel(const tlsrec_stream_out *s, uint32_t n, const SlotState *slots, uint32_t cap,
-                                      uint32_t *counts, unsigned long long *bytes)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long b = 0;
-    if (i < n) {
-        const uint32_t f = frag_of(s[i]);
-        const OutShape sh = out_shape(slots, cap, s[i].slot);
-        const bool ok = sh.ok && !sh.tls13;
-        counts[i] = ok ? (uint32_t) (((uint64_t) s[i].in_len + f - 1) / f) : 0u;
-        b = ok ? s[i].in_len : 0;
-    } else if (i == n) {
-        counts[n] = 0;
-    }
-    wave_add_bytes(bytes, b);
-}
-
-__device__ __forceinline__ void dtls_seq(uint8_t ctr[8], const uint8_t base[8], uint64_t k)
-{
-    const uint64_t s = (ReplayWindow::seq48(base) + k) & 0xFFFFFFFFFFFFull;
-    ctr[0] = base[0];
-    ctr[1] = base[1];
-#pragma unroll
-    for (int b = 7; b >= 2; b--) ctr[b] = (uint8_t) (s >> (8 * (7 - b)));
-}
-
-/* One wave per record: the DTLS header (type after encryption, FE FD, epoch +
- * sequence, out_cid, protected length; mbedtls_ssl_write_record :2669-2727),
- * the descriptor, and the plaintext copied behind the header -- or, with
- * srcoff (nothing to copy), one thread per record (LPR = 1, as
- * out_frame_kernel). */
-template <int LPR>
-__device__ __forceinline__ void dtls_out_frame_one(const tlsrec_stream_out &si, uint32_t k, uint32_t j, uint32_t lane,
-                                                   const SlotState *slots, uint32_t cap, const uint8_t *in,
-                                                   uint8_t *out, tlsrec_batch_rec *recs, uint64_t *srcoff)
-{
-    const uint32_t f = frag_of(si);
-    const OutShape sh = out_shape(slots, cap, si.slot);
-    const uint32_t cid = dtls_cid_of(slots, si.slot), hdr = 13 + cid;
-    const uint64_t src_off = (uint64_t) k * f;
-    const uint64_t left = (uint64_t) si.in_len - src_off;
-    const uint32_t len = left < f ? (uint32_t) left : f;
-    const uint64_t pos = si.out_off + (uint64_t) k * (hdr + dtls_body(sh, cid, f));
-    /* past the 48-bit wrap (:2741-2756): never protected, no bytes written --
-     * record k would reuse sequence number (epoch, k - wrap), i.e. a nonce */
-    if ((uint64_t) k > 0xFFFFFFFFFFFFull - ReplayWindow::seq48(si.out_ctr)) {
-        if (lane == 0) {
-            tlsrec_batch_rec d;
-            memset(&d, 0, sizeof(d));
-            d.slot = NO_SLOT;
-            recs[j] = d;
-        }
-        return;
-    }
-    if (srcoff) {                                 /* (out_frame_kernel) */
-        if (lane == 0) srcoff[j] = si.in_off + src_off;
-    } else {
-        const uint8_t *src = in + si.in_off + src_off;
-        uint8_t *dst = out + pos + hdr + sh.head;
-        const uint32_t nv = len / 16;
-        for (uint32_t v = lane; v < nv; v += LPR) {
-            uint4 w;
-            __builtin_memcpy(&w, src + 16 * v, 16);
-            __builtin_memcpy(dst + 16 * v, &w, 16);
-        }
-        for (uint32_t b = nv * 16 + lane; b < len; b += LPR) dst[b] = src[b];
-    }
-    if (lane == 0) {
-        const uint32_t body = dtls_body(sh, cid, len);
-        uint8_t *h = out + pos;
-        tlsrec_batch_rec d;
-        memset(&d, 0, sizeof(d));
-        dtls_seq(d.ctr, si.out_ctr, k);
-        h[0] = cid ? (uint8_t) TLSREC_MSG_CID : si.type;     /* the type encrypt_buf leaves (:2727) */
-        h[1] = 0xfe;                                          /* mbedtls_ssl_write_version, DTLS 1.2 */
-        h[2] = 0xfd;
-        memcpy(h + 3, d.ctr, 8);
-        memcpy(h + 11, slots[si.slot].cid, cid);              /* out_cid (:2712-2714) */
-        h[11 + cid] = (uint8_t) (body >> 8);
-        h[12 + cid] = (uint8_t) body;
-        d.buf_off = pos + hdr;                                /* rec.buf = out_iv */
-        d.buf_len = TLSREC_DTLS_OUT_BUFFER_LEN - hdr;         /* out_buf_len - (out_iv - out_buf) */
-        d.data_offset = sh.head;
-        d.data_len = len;
-        d.slot = si.slot;
-        d.type = si.type;
-        d.ver[0] = 0xfe;
-        d.ver[1] = 0xfd;
-        recs[j] = d;
-    }
-}
-
-template <int LPR>
-__global__ void __launch_bounds__(256) dtls_out_frame_kernel(const tlsrec_stream_out *s, uint32_t n,
-                                                             const uint32_t *offs, uint32_t total,
-                                                             const SlotState *slots, uint32_t cap, const uint8_t *in,
-                                                             uint8_t *out, tlsrec_batch_rec *recs, uint64_t *srcoff)
-{
-    const uint32_t j = blockIdx.x * (256 / LPR) + threadIdx.x / LPR, lane = threadIdx.x % LPR;
-    if (j >= total) return;
-    const uint32_t i = recs[j].slot;              /* connection of record j (out_map_kernel) */
-    dtls_out_frame_one<LPR>(s[i], j - offs[i], j, lane, slots, cap, in, out, recs, srcoff);
-}
-
-/* (r06) The in-place send frame (srcoff) with a group of RG lanes per
- * connection: lane q frames records q, q + RG, ... of its connection, so no
- * out_map pass has to tell each record its connection (a 4-byte write into
- * every descriptor, 17-37 us of a 1 M-record send) and a connection's
- * descriptor is read once per group, not once per record. */
-template <bool DTLS>
-__global__ void __launch_bounds__(RX_THREADS) out_frame_conn_kernel(const tlsrec_stream_out *s, uint32_t n,
-                                                                    const uint32_t *offs, const uint32_t *counts,
-                                                                    const SlotState *slots, uint32_t cap,
-                                                                    const uint8_t *in, uint8_t *out,
-                                                                    tlsrec_batch_rec *recs, uint64_t *srcoff)
-{
-    const uint32_t i = blockIdx.x * RX_CONNS + threadIdx.x / RG, q = threadIdx.x % RG;
-    if (i >= n) return;
-    const tlsrec_stream_out si = s[i];
-    const uint32_t first = offs[i], c = counts[i];
-    for (uint32_t k = q; k < c; k += RG) {
-        if constexpr (DTLS)
-            dtls_out_frame_one<1>(si, k, first + k, 0, slots, cap, in, out, recs, srcoff);
-        else
-            out_frame_one<1>(si, k, first + k, 0, slots, cap, in, out, recs, srcoff);
-    }
-}
-
-__global__ void dtls_out_finish_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs,
-                                       const uint32_t *counts, const SlotState *slots, uint32_t cap,
-                                       const tlsrec_batch_res *res, tlsrec_stream_out_res *sres)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const tlsrec_stream_out si = s[i];
-    const OutShape sh = out_shape(slots, cap, si.slot);
-    int32_t st = (sh.ok && !sh.tls13) || si.in_len == 0 ? 0 : TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    const uint32_t cid = sh.ok ? dtls_cid_of(slots, si.slot) : 0, f = frag_of(si);
-    uint8_t ctr[8];
-    memcpy(ctr, si.out_ctr, 8);
-    uint32_t nrec = 0, olen = 0;
-    const uint32_t first = offs[i], cnt = counts[i];
-    for (uint32_t k = 0; k < cnt && st == 0; k++) {
-        const tlsrec_batch_res &r = res[first + k];
-        if (r.status) { st = r.status; break; }
-        const uint64_t left = (uint64_t) si.in_len - (uint64_t) k * f;
-        const uint32_t len = left < f ? (uint32_t) left : f;
-        if (r.data_offset != 0 || r.data_len != dtls_body(sh, cid, len)) {          /* :2697-2700 */
-            st = TLSREC_ERR_SSL_INTERNAL_ERROR;
-            break;
-        }
-        olen += 13 + cid + r.data_len;
-        nrec++;
-        int b;                                                 /* :2741-2756, ep_len = 2 */
-        for (b = 8; b > 2; b--)
-            if (++ctr[b - 1] != 0) break;
-        if (b == 2) st = TLSREC_ERR_SSL_COUNTER_WRAPPING;
-    }
-    tlsrec_stream_out_res o;
-    memset(&o, 0, sizeof(o));
-    o.status = st;
-    o.first = first;
-    o.nrec = nrec;
-    o.out_len = olen;
-    memcpy(o.out_ctr, ctr, 8);
-    o.nparsed = cnt;
-    sres[i] = o;
-}
-
 /* The batch's record count and byte total to the host (r06): one wave sums
  * the spread byte counters and writes both into the calling thread's
  * host-mapped mailbox, then the call's sequence number after a release
@@ -1641,72 +1578,54 @@ struct Scratch {
 };
 }
 
-/* TLSREC_RX_FUSED=0: the DTLS receive framing as count, scan and emit
- * kernels (r05 / early r06), kept for A/B runs and as the tests' second path;
- * TLSREC_RX_FUSED_STREAM=1: the stream receive framing in one pass (measured
- * slower than its three kernels) */
-static bool fused_env(void)
+/* The environment switches of this file, read on every call (the tests flip
+ * them between calls).  All but the last are the default path against an
+ * older or alternative one kept for A/B runs and as the tests' second path:
+ *   TLSREC_RX_FUSED=0         DTLS receive framing as count, scan and emit
+ *                             kernels (r05 / early r06) instead of one pass
+ *   TLSREC_RX_FUSED_STREAM=1  stream receive framing in one pass (measured
+ *                             slower than its three kernels)
+ *   TLSREC_RX_GROUPWALK=0     the r05 stream receive framing: one lane per
+ *                             connection in the count and emit kernels
+ *   TLSREC_DTLS_STASH=0       the DTLS frame kernel's emit walks the headers
+ *                             again instead of reading the count walk's LDS copy
+ *   TLSREC_RX_PREFILL=0       the receive batch runs its guard kernel although
+ *                             the emit kernels wrote the guard results
+ *   TLSREC_RX_MAILBOX=0       the totals come back by two copies and a stream
+ *                             synchronize (before r06's second session)
+ *   TLSREC_STREAM_SRC=0       the send paths copy the application data into
+ *                             the output stream first (r04) instead of reading
+ *                             it in place (r05)
+ *   TLSREC_RX_RG=4|8|16       forces rx_group()'s lanes per connection */
+static bool env_flag(const char *name, bool dflt)
 {
-    const char *e = getenv("TLSREC_RX_FUSED");
-    return !(e && atoi(e) == 0);
+    const char *e = getenv(name);
+    return e ? atoi(e) != 0 : dflt;
 }
-/* TLSREC_DTLS_STASH=0: the DTLS frame kernel's emit walks the headers again
- * instead of reading the count walk's LDS copy (A/B runs) */
-static bool dtls_stash_env(void)
+static int env_int(const char *name)
 {
-    const char *e = getenv("TLSREC_DTLS_STASH");
-    return !(e && atoi(e) == 0);
+    const char *e = getenv(name);
+    return e ? atoi(e) : 0;
 }
-/* TLSREC_RX_PREFILL=0: the receive batch runs its guard kernel although the
- * emit kernels wrote the guard results (A/B runs) */
-static int prefill_env(void)
-{
-    const char *e = getenv("TLSREC_RX_PREFILL");
-    return (e && atoi(e) == 0) ? 0 : 1;
-}
+
 /* lanes per connection of the receive header walk: the records a
  * connection can hold on average by the caller's capacity (max_records /
  * connections) -- 4, 8 or 16; TLSREC_RX_RG forces one */
 static int rx_group(uint32_t n, uint32_t max_records)
 {
-    const char *e = getenv("TLSREC_RX_RG");
-    if (e) {
-        const int g = atoi(e);
-        if (g == 4 || g == 8 || g == 16) return g;
-    }
+    const int g = env_int("TLSREC_RX_RG");
+    if (g == 4 || g == 8 || g == 16) return g;
     const uint64_t per = n ? ((uint64_t) max_records + n - 1) / n : 16;
     return per <= 4 ? 4 : (per <= 8 ? 8 : 16);
 }
 
-template <int G>
-static void launch_rx_count(uint32_t n, hipStream_t st, const tlsrec_stream_in *s, const uint8_t *arena,
-                            uint32_t *counts, HdrStop *stops, unsigned long long *bytes)
+/* f(std::integral_constant<int, g>) for the lane-group kernels' template argument */
+template <typename F>
+static void with_rx_group(int g, F f)
 {
-    hipLaunchKernelGGL(in_count_group_kernel<G>, dim3((n + 1 + RX_THREADS / G - 1) / (RX_THREADS / G)),
-                       dim3(RX_THREADS), 0, st, s, n, arena, counts, stops, bytes);
-}
-
-template <int G>
-static void launch_rx_emit(uint32_t n, hipStream_t st, const tlsrec_stream_in *s, const uint8_t *arena,
-                           const uint32_t *offs, const SlotState *slots, uint32_t cap, tlsrec_batch_rec *recs,
-                           uint32_t max_records, tlsrec_batch_res *res)
-{
-    hipLaunchKernelGGL(in_emit_group_kernel<G>, dim3((n + RX_THREADS / G - 1) / (RX_THREADS / G)), dim3(RX_THREADS),
-                       0, st, s, n, arena, offs, slots, cap, recs, max_records, res);
-}
-
-static bool fused_stream_env(void)
-{
-    const char *e = getenv("TLSREC_RX_FUSED_STREAM");
-    return e && atoi(e) != 0;
-}
-
-/* the send paths read the application data in place (r05; TLSREC_STREAM_SRC=0
- * copies it into the output stream first, as r04 did) */
-static bool src_env(void)
-{
-    const char *e = getenv("TLSREC_STREAM_SRC");
-    return !(e && atoi(e) == 0);
+    if (g == 4) f(std::integral_constant<int, 4>{});
+    else if (g == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
 }
 
 /* tiles: the one-pass framing kernels' tile status words (0 = none) */
@@ -1741,20 +1660,12 @@ struct Mailbox {
 thread_local Mailbox t_mbox;
 }
 
-/* TLSREC_RX_MAILBOX=0: the totals come back by two copies and a stream
- * synchronize (before r06's second session), for A/B runs */
-static bool mailbox_env(void)
-{
-    const char *e = getenv("TLSREC_RX_MAILBOX");
-    return !(e && atoi(e) == 0);
-}
-
 /* the calling thread's mailbox (device pointer) and the next sequence
  * number; null with the copy path (TLSREC_RX_MAILBOX=0) or no mailbox */
 static TotMbox *mailbox_next(uint64_t *seq)
 {
     *seq = 0;
-    if (!mailbox_env()) return nullptr;
+    if (!env_flag("TLSREC_RX_MAILBOX", true)) return nullptr;
     Mailbox &m = t_mbox;
     if (!m.h) {
         void *h = nullptr, *d = nullptr;
@@ -1828,15 +1739,6 @@ static int fetch_total(Scratch &sc, uint32_t n, hipStream_t st, uint32_t *total,
     return r ? r : collect_totals(sc, n, st, seq, total, avg_bytes);
 }
 
-/* TLSREC_RX_GROUPWALK=0: the r05 receive framing (one lane per connection
- * in the count and emit kernels), kept for A/B runs and as the tests' second
- * path */
-static bool groupwalk_env(void)
-{
-    const char *e = getenv("TLSREC_RX_GROUPWALK");
-    return !(e && atoi(e) == 0);
-}
-
 /* exclusive scan of counts[0..n] -> offs, and the totals queued to the
  * mailbox (*seq, see publish_totals): collect them with collect_totals */
 static int scan_publish(Scratch &sc, uint32_t n, hipStream_t st, uint64_t *seq)
@@ -1869,71 +1771,61 @@ extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_strea
     const SlotState *slots = tlsrec__keytab_slots(kt);
     const uint32_t cap = tlsrec_keytab_capacity(kt);
     Scratch sc;
-    const bool fused = fused_stream_env() && groupwalk_env();
+    const bool gw = env_flag("TLSREC_RX_GROUPWALK", true);
+    const bool fused = env_flag("TLSREC_RX_FUSED_STREAM", false) && gw;
     /* one pass: G lanes per connection, tiles of 512 connections (G = 4:
      * two chunks of 128) or 128 (G = 16: eight chunks of 16) */
-    const int frg = rx_group(nstreams, max_records);
-    const uint32_t ftile = frg == 4 ? 2u * 64u : (frg == 8 ? 4u * 32u : 8u * 16u);
+    const int rg = rx_group(nstreams, max_records);
+    const uint32_t ftile = rg == 4 ? 2u * 64u : (rg == 8 ? 4u * 32u : 8u * 16u);
     const uint32_t tiles = blocks(nstreams, ftile);
     int r = scratch_alloc(sc, nstreams, st, fused ? tiles : 0u);
     uint32_t total = 0, avg = 0;
-    const bool gw = groupwalk_env();
-    TLSREC_LAUNCH_LOG(TLSREC_LOG_STREAM_RX_FRAME, fused, gw ? frg : 1, 0, 0);
+    const uint8_t *ar = arena;
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_STREAM_RX_FRAME, fused, gw ? rg : 1, 0, 0);
     if (r == 0 && fused) {
         /* count, scan and emit in one pass (descriptors up to max_records) */
         /* tiles of 128 connections: one chunk of 128 at 4 lanes (512 threads),
          * or chunks of 64 / 32 at 8 / 16 lanes */
-        constexpr int FNT = TLSREC_RX_FRAME_NT;
-        if (frg == 4)
-            hipLaunchKernelGGL((in_frame_kernel<4, 512 / FNT, FNT>), dim3(tiles), dim3(FNT), 0, st, streams, nstreams,
-                               (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes, sc.tstat,
-                               sc.tctr, recs, (recs && res) ? max_records : 0u, res);
-        else if (frg == 8)
-            hipLaunchKernelGGL((in_frame_kernel<8, 1024 / FNT, FNT>), dim3(tiles), dim3(FNT), 0, st, streams,
-                               nstreams, (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes,
-                               sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res);
-        else
-            hipLaunchKernelGGL((in_frame_kernel<16, 2048 / FNT, FNT>), dim3(tiles), dim3(FNT), 0, st, streams,
-                               nstreams, (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes,
-                               sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res);
+        with_rx_group(rg, [&](auto G) {
+            constexpr int FNT = TLSREC_RX_FRAME_NT;
+            hipLaunchKernelGGL((in_frame_kernel<G(), (G() * 128) / FNT, FNT>), dim3(tiles), dim3(FNT), 0, st, streams,
+                               nstreams, ar, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes, sc.tstat, sc.tctr,
+                               recs, (recs && res) ? max_records : 0u, res);
+        });
         r = hipGetLastError() == hipSuccess ? fetch_total(sc, nstreams, st, &total, &avg)
                                             : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     } else if (r == 0) {
-        const int rg = rx_group(nstreams, max_records);
-        if (gw) {
-            if (rg == 4)
-                launch_rx_count<4>(nstreams, st, streams, (const uint8_t *) arena, sc.counts, sc.stops, sc.bytes);
-            else if (rg == 8)
-                launch_rx_count<8>(nstreams, st, streams, (const uint8_t *) arena, sc.counts, sc.stops, sc.bytes);
-            else
-                launch_rx_count<16>(nstreams, st, streams, (const uint8_t *) arena, sc.counts, sc.stops, sc.bytes);
-        } else
+        if (gw)
+            with_rx_group(rg, [&](auto G) {
+                hipLaunchKernelGGL(in_count_group_kernel<G()>, dim3(blocks(nstreams + 1, RX_THREADS / G())),
+                                   dim3(RX_THREADS), 0, st, streams, nstreams, ar, sc.counts, sc.stops, sc.bytes);
+            });
+        else
             hipLaunchKernelGGL(in_count_kernel, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams, nstreams,
-                               (const uint8_t *) arena, sc.counts, sc.stops, sc.bytes);
+                               ar, sc.counts, sc.stops, sc.bytes);
         uint64_t seq = 0;
         r = hipGetLastError() == hipSuccess ? scan_publish(sc, nstreams, st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         /* the descriptors are emitted while the host collects the totals
          * (r06; at most max_records of them: the check follows) */
         if (r == 0 && recs && res) {
-            if (gw && rg == 4)
-                launch_rx_emit<4>(nstreams, st, streams, (const uint8_t *) arena, sc.offs, slots, cap, recs,
-                                  max_records, res);
-            else if (gw && rg == 8)
-                launch_rx_emit<8>(nstreams, st, streams, (const uint8_t *) arena, sc.offs, slots, cap, recs,
-                                  max_records, res);
-            else if (gw)
-                launch_rx_emit<16>(nstreams, st, streams, (const uint8_t *) arena, sc.offs, slots, cap, recs,
-                                   max_records, res);
+            if (gw)
+                with_rx_group(rg, [&](auto G) {
+                    hipLaunchKernelGGL(in_emit_group_kernel<G()>, dim3(blocks(nstreams, RX_THREADS / G())),
+                                       dim3(RX_THREADS), 0, st, streams, nstreams, ar, sc.offs, slots, cap, recs,
+                                       max_records, res);
+                });
             else
                 hipLaunchKernelGGL(in_emit_kernel, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
-                                   (const uint8_t *) arena, sc.offs, slots, cap, recs, max_records, res);
+                                   ar, sc.offs, slots, cap, recs, max_records, res);
             if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         }
         if (r == 0) r = collect_totals(sc, nstreams, st, seq, &total, &avg);
     }
     if (r == 0 && total > max_records) r = TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
     if (r == 0 && total && (!recs || !res)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (r == 0 && total) r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg, prefill_env());
+    if (r == 0 && total)
+        r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg,
+                                env_flag("TLSREC_RX_PREFILL", true));
     if (r == 0) {
         hipLaunchKernelGGL(in_finish_kernel, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams, sc.offs,
                            sc.counts, sc.stops, slots, cap, recs, res, sres);
@@ -1944,30 +1836,42 @@ extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_strea
     return r;
 }
 
+/* the output bytes of in_len application bytes: records of max_frag bytes,
+ * each a header of hdr bytes and W::body() -- the kernels' arithmetic */
+template <typename W>
+static uint64_t send_out_size(uint64_t hdr, uint64_t head, uint64_t tag, uint32_t granularity, bool padded,
+                              uint64_t in_len, uint32_t max_frag)
+{
+    const uint64_t f = max_frag ? max_frag : 16384, g = granularity ? granularity : 16;
+    const uint64_t full = in_len / f, rest = in_len % f;
+    return full * (hdr + W::body(head, tag, g, padded, f)) + (rest ? hdr + W::body(head, tag, g, padded, rest) : 0);
+}
+
 extern "C" uint64_t tlsrec_stream_out_size(int tls_version, int cipher, uint32_t granularity, uint64_t in_len,
                                            uint32_t max_frag)
 {
     if (tlsrec_cipher_keylen(cipher) == 0) return 0;
-    const uint64_t tag = tlsrec_cipher_taglen(cipher);
     if (tls_version != TLSREC_VERSION_TLS1_2 && tls_version != TLSREC_VERSION_TLS1_3) return 0;
-    const uint64_t f = max_frag ? max_frag : 16384;
-    const uint64_t g = granularity ? granularity : 16;
     const uint64_t head = (tls_version == TLSREC_VERSION_TLS1_2 && cipher != TLSREC_CIPHER_CHACHA20_POLY1305) ? 8 : 0;
-    auto body = [&](uint64_t n) -> uint64_t {
-        if (tls_version == TLSREC_VERSION_TLS1_3) {
-            const uint64_t inner = n + 1;
-            return inner + (g - inner % g) % g + tag;
-        }
-        return head + n + tag;
-    };
-    const uint64_t full = in_len / f, rest = in_len % f;
-    return full * (5 + body(f)) + (rest ? 5 + body(rest) : 0);
+    return send_out_size<TlsWire>(5, head, tlsrec_cipher_taglen(cipher), granularity,
+                                  tls_version == TLSREC_VERSION_TLS1_3, in_len, max_frag);
 }
 
-extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
-                                     const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
-                                     tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
-                                     uint32_t *nrecords, void *stream)
+extern "C" uint64_t tlsrec_dtls_out_size(int cipher, uint32_t granularity, uint32_t cid_len, uint64_t in_len,
+                                         uint32_t max_frag)
+{
+    if (tlsrec_cipher_keylen(cipher) == 0 || cid_len > TLSREC_CID_LEN_MAX) return 0;
+    const uint64_t head = cipher != TLSREC_CIPHER_CHACHA20_POLY1305 ? 8 : 0;
+    return send_out_size<DtlsWire>(13 + cid_len, head, tlsrec_cipher_taglen(cipher), granularity, cid_len != 0, in_len,
+                                   max_frag);
+}
+
+/* tlsrec_stream_encrypt / tlsrec_dtls_encrypt: count, scan, frame, the AEAD
+ * batch, finish -- the same kernels over the wire format W */
+template <typename W>
+static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                     const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
+                     uint32_t max_records, tlsrec_stream_out_res *sres, uint32_t *nrecords, void *stream)
 {
     if (nrecords) *nrecords = 0;
     if (!kt || (nstreams && (!streams || !in_arena || !out_arena || !sres))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
@@ -1979,7 +1883,7 @@ extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_strea
     int r = scratch_alloc(sc, nstreams, st);
     uint32_t total = 0, avg = 0;
     if (r == 0) {
-        hipLaunchKernelGGL(out_count_kernel, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams, nstreams,
+        hipLaunchKernelGGL(send_count_kernel<W>, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams, nstreams,
                            slots, cap, sc.counts, sc.bytes);
         r = hipGetLastError() == hipSuccess ? scan_total(sc, nstreams, st, &total, &avg)
                                             : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
@@ -1991,17 +1895,18 @@ extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_strea
          * data in place (tlsrec__batch_src); other AEADs: copy, then in place */
         uint64_t *srcoff = nullptr;
         tlsrec_scratch_lease sl = { nullptr, nullptr };
-        if (tlsrec__keytab_src_ok(kt) && src_env() &&
+        if (tlsrec__keytab_src_ok(kt) && env_flag("TLSREC_STREAM_SRC", true) &&
             tlsrec__scratch_acquire(st, 3, (size_t) total * sizeof(uint64_t), &sl) == 0)
             srcoff = (uint64_t *) sl.mem;
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_SEND_FRAME, srcoff != nullptr, 0, 0, 0);
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_SEND_FRAME, srcoff != nullptr, W::LOG_P1, 0, 0);
+        /* (a skewed batch serialises on its longest connection here: ADVICE.md, first item) */
         if (srcoff) {
-            hipLaunchKernelGGL(out_frame_conn_kernel<false>, dim3(blocks(nstreams, RX_CONNS)), dim3(RX_THREADS), 0, st,
+            hipLaunchKernelGGL(out_frame_conn_kernel<W>, dim3(blocks(nstreams, RX_CONNS)), dim3(RX_THREADS), 0, st,
                                streams, nstreams, sc.offs, sc.counts, slots, cap, in_arena, out_arena, recs, srcoff);
         } else {
             hipLaunchKernelGGL(out_map_kernel, dim3(blocks(nstreams, 4)), dim3(256), 0, st, nstreams, sc.offs,
                                sc.counts, recs);
-            hipLaunchKernelGGL(out_frame_kernel<64>, dim3(blocks(total, 4)), dim3(256), 0, st, streams, nstreams,
+            hipLaunchKernelGGL((send_frame_kernel<W, 64>), dim3(blocks(total, 4)), dim3(256), 0, st, streams, nstreams,
                                sc.offs, total, slots, cap, in_arena, out_arena, recs, srcoff);
         }
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
@@ -2011,13 +1916,29 @@ extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_strea
         if (srcoff) tlsrec__scratch_release(&sl);
     }
     if (r == 0) {
-        hipLaunchKernelGGL(out_finish_kernel, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
+        hipLaunchKernelGGL(send_finish_kernel<W>, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
                            sc.offs, sc.counts, slots, cap, res, sres);
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     tlsrec__scratch_release(&sc.lease);
     if (r == 0 && nrecords) *nrecords = total;
     return r;
+}
+
+extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                                     const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
+                                     tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
+                                     uint32_t *nrecords, void *stream)
+{
+    return send_impl<TlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream);
+}
+
+extern "C" int tlsrec_dtls_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                                   const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
+                                   tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
+                                   uint32_t *nrecords, void *stream)
+{
+    return send_impl<DtlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream);
 }
 
 extern "C" int tlsrec_stream_read(const tlsrec_stream_in_res *sres, uint32_t nstreams, const tlsrec_batch_rec *recs,
@@ -2044,7 +1965,7 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
     const SlotState *slots = tlsrec__keytab_slots(kt);
     const uint32_t cap = tlsrec_keytab_capacity(kt);
     Scratch sc;
-    const bool fused = fused_env();
+    const bool fused = env_flag("TLSREC_RX_FUSED", true);
     const uint32_t tiles = blocks(nconns, DG_THREADS);
     int r = scratch_alloc(sc, nconns, st, fused ? tiles : 0u);
     uint32_t total = 0, avg = 0;
@@ -2069,7 +1990,7 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
                            hipLaunchKernelGGL(dtls_frame_kernel<S_>, dim3(tiles), dim3(DG_THREADS), 0, st, conns, \
                            nconns, dgrams, ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.bytes, \
                            sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst); } while (0)
-        if (!dtls_stash_env() || per > 16) TLSREC_DTLS_FRAME(0);
+        if (!env_flag("TLSREC_DTLS_STASH", true) || per > 16) TLSREC_DTLS_FRAME(0);
         else if (per > 4) TLSREC_DTLS_FRAME(16);
         else TLSREC_DTLS_FRAME(4);
 #undef TLSREC_DTLS_FRAME
@@ -2091,7 +2012,9 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
     }
     if (r == 0 && total > max_records) r = TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
     if (r == 0 && total && (!recs || !res || !disp)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (r == 0 && total) r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg, prefill_env());
+    if (r == 0 && total)
+        r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg,
+                                env_flag("TLSREC_RX_PREFILL", true));
     if (r == 0) {
         if (fused)
             hipLaunchKernelGGL(dtls_finish_kernel<true>, dim3(blocks(nconns, 256)), dim3(256), 0, st, conns, nconns,
@@ -2103,81 +2026,6 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     if (dgl.mem) tlsrec__scratch_release(&dgl);
-    tlsrec__scratch_release(&sc.lease);
-    if (r == 0 && nrecords) *nrecords = total;
-    return r;
-}
-
-extern "C" uint64_t tlsrec_dtls_out_size(int cipher, uint32_t granularity, uint32_t cid_len, uint64_t in_len,
-                                         uint32_t max_frag)
-{
-    if (tlsrec_cipher_keylen(cipher) == 0 || cid_len > TLSREC_CID_LEN_MAX) return 0;
-    const uint64_t tag = tlsrec_cipher_taglen(cipher);
-    const uint64_t f = max_frag ? max_frag : 16384;
-    const uint64_t g = granularity ? granularity : 16;
-    const uint64_t head = cipher != TLSREC_CIPHER_CHACHA20_POLY1305 ? 8 : 0;
-    auto body = [&](uint64_t n) -> uint64_t {
-        if (cid_len) {
-            const uint64_t inner = n + 1;
-            return head + inner + (g - inner % g) % g + tag;
-        }
-        return head + n + tag;
-    };
-    const uint64_t full = in_len / f, rest = in_len % f;
-    return full * (13 + cid_len + body(f)) + (rest ? 13 + cid_len + body(rest) : 0);
-}
-
-extern "C" int tlsrec_dtls_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
-                                   const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
-                                   tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
-                                   uint32_t *nrecords, void *stream)
-{
-    if (nrecords) *nrecords = 0;
-    if (!kt || (nstreams && (!streams || !in_arena || !out_arena || !sres))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (nstreams == 0) return 0;
-    hipStream_t st = (hipStream_t) stream;
-    const SlotState *slots = tlsrec__keytab_slots(kt);
-    const uint32_t cap = tlsrec_keytab_capacity(kt);
-    Scratch sc;
-    int r = scratch_alloc(sc, nstreams, st);
-    uint32_t total = 0, avg = 0;
-    if (r == 0) {
-        hipLaunchKernelGGL(dtls_out_count_kernel, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams, nstreams,
-                           slots, cap, sc.counts, sc.bytes);
-        r = hipGetLastError() == hipSuccess ? scan_total(sc, nstreams, st, &total, &avg)
-                                            : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    if (r == 0 && total > max_records) r = TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
-    if (r == 0 && total && (!recs || !res)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (r == 0 && total) {
-        /* AES-GCM / ChaCha20-Poly1305 tables: the AEAD reads the application
-         * data in place (tlsrec__batch_src); other AEADs: copy, then in place */
-        uint64_t *srcoff = nullptr;
-        tlsrec_scratch_lease sl = { nullptr, nullptr };
-        if (tlsrec__keytab_src_ok(kt) && src_env() &&
-            tlsrec__scratch_acquire(st, 3, (size_t) total * sizeof(uint64_t), &sl) == 0)
-            srcoff = (uint64_t *) sl.mem;
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_SEND_FRAME, srcoff != nullptr, 1, 0, 0);
-        if (srcoff) {
-            hipLaunchKernelGGL(out_frame_conn_kernel<true>, dim3(blocks(nstreams, RX_CONNS)), dim3(RX_THREADS), 0, st,
-                               streams, nstreams, sc.offs, sc.counts, slots, cap, in_arena, out_arena, recs, srcoff);
-        } else {
-            hipLaunchKernelGGL(out_map_kernel, dim3(blocks(nstreams, 4)), dim3(256), 0, st, nstreams, sc.offs,
-                               sc.counts, recs);
-            hipLaunchKernelGGL(dtls_out_frame_kernel<64>, dim3(blocks(total, 4)), dim3(256), 0, st, streams, nstreams,
-                               sc.offs, total, slots, cap, in_arena, out_arena, recs, srcoff);
-        }
-        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-        if (r == 0)
-            r = srcoff ? tlsrec__batch_src(kt, recs, res, total, in_arena, out_arena, stream, avg, srcoff)
-                       : tlsrec__batch_sized(kt, recs, res, total, out_arena, out_arena, stream, 0, avg, 0);
-        if (srcoff) tlsrec__scratch_release(&sl);
-    }
-    if (r == 0) {
-        hipLaunchKernelGGL(dtls_out_finish_kernel, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
-                           sc.offs, sc.counts, slots, cap, res, sres);
-        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
     tlsrec__scratch_release(&sc.lease);
     if (r == 0 && nrecords) *nrecords = total;
     return r;

@@ -222,8 +222,9 @@ hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream
  *   CHACHA          p0 lanes per record, p1 src_off set
  *   ALT_GCM / CCM   p0 the cipher / the nr mask
  *   BUCKET          p0 1 = bucket pass taken, 0 = identity order
- *   SEND_FRAME      p0 1 = out_frame_conn_kernel (contents read in place),
- *                   0 = map + out_frame_kernel<64> (copied); p1 1 = DTLS
+ *   SEND_FRAME      p0 1 = out_frame_conn_kernel<W> (contents read in place),
+ *                   0 = map + send_frame_kernel<W, 64> (copied); p1 1 = DTLS
+ *                   (W = DtlsWire, else TlsWire)
  *   DTLS_RX_FRAME   p0 the stash depth S of dtls_frame_kernel (4 / 16 / 0),
  *                   -1 = count, scan and emit kernels
  *   STREAM_RX_FRAME p0 1 = one pass, 0 = three kernels; p1 lanes per

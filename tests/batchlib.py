@@ -337,19 +337,22 @@ class Table:
     keys; a slot with a CID is one direction (its out_cid when sending, in_cid
     when receiving)."""
 
-    def __init__(self, slots, tls=M.VERSION_TLS1_2, tls_of=None):
-        """tls_of: {slot: version} for single slots that differ from `tls`"""
+    def __init__(self, slots, tls=M.VERSION_TLS1_2, tls_of=None, gran_of=None):
+        """tls_of: {slot: version} for single slots that differ from `tls`;
+        gran_of: {slot: padding granularity} (default 0 = 16)"""
         import torch
         self.slots = slots
         tls_of = tls_of or {}
+        self.gran_of = gran_of or {}
         self.kt = M.KeyTable(len(slots))
-        self.kt.load(np.concatenate([M.key_material(c, tls_of.get(s, tls), k, iv)
+        self.kt.load(np.concatenate([M.key_material(c, tls_of.get(s, tls), k, iv, self.gran_of.get(s, 0))
                                      for s, (c, k, iv, _) in enumerate(slots)]))
         self.ot = []
         for s, (c, k, iv, cid) in enumerate(slots):
             if cid:
                 self.kt.set_cid(s, cid)
-            t = O.Transform(O.TLS1_2 if tls_of.get(s, tls) == M.VERSION_TLS1_2 else O.TLS1_3, c, k, k, iv, iv)
+            t = O.Transform(O.TLS1_2 if tls_of.get(s, tls) == M.VERSION_TLS1_2 else O.TLS1_3, c, k, k, iv, iv,
+                            granularity=self.gran_of.get(s, 0) or 16)
             t.set_cid(cid, cid)
             self.ot.append(t)
         torch.cuda.synchronize()
@@ -360,7 +363,8 @@ class Table:
         import torch
         from mbedtls_amd import dtls as D
         from mbedtls_amd import stream as S
-        sizes = [D.out_size(self.slots[j[0]][0], 0, len(self.slots[j[0]][3]), len(j[1]), j[3]) for j in jobs]
+        sizes = [D.out_size(self.slots[j[0]][0], self.gran_of.get(j[0], 0), len(self.slots[j[0]][3]), len(j[1]), j[3])
+                 for j in jobs]
         d, ina, outs, pos_out, nmax = _send_layout(jobs, sizes, odd)
         dev = torch.device("cuda")
         tin = torch.from_numpy(ina).to(dev)

@@ -1,7 +1,8 @@
 """The in-place send path (the default of tlsrec_stream_encrypt /
 tlsrec_dtls_encrypt for tables of AES-GCM and ChaCha20-Poly1305 keys without
-CIDs: out_frame_conn_kernel, then the AEAD kernels read each record's content
-at in + src_off[i]) against the oracle, byte for byte: record edges and odd
+CIDs: out_frame_conn_kernel<TlsWire / DtlsWire>, then the AEAD kernels read
+each record's content at in + src_off[i]) against the oracle, byte for byte;
+both calls are send_impl<W> over one set of kernels: record edges and odd
 input offsets, few connections of many records, and every launch shape the
 engine picks with src_off set.  Each test asserts its path from the
 dispatchers' launch log; shapes are sized from the device's CU count by the
@@ -71,6 +72,11 @@ def _assert_in_place(log, dtls, in_place=True):
     assert aead and not log(_abi.LOG_ALT_GCM) and not log(_abi.LOG_CCM)
     assert all(e[4] == int(in_place) for e in log(_abi.LOG_GCM)), log()
     assert all(e[2] == int(in_place) for e in log(_abi.LOG_CHACHA)), log()
+
+
+def _assert_copy_frame(log, dtls):
+    """the send frame of a call whose table holds a CCM key or a CID: map + copy"""
+    assert log(_abi.LOG_SEND_FRAME) == [(_abi.LOG_SEND_FRAME, 0, int(dtls), 0, 0)], log()
 
 
 # ---- 1. edges ---------------------------------------------------------------------
@@ -273,3 +279,51 @@ def test_launch_shape_with_src_off(case, monkeypatch, launch_log):
     assert sum(int(g[0]["nrec"]) for g in got) == n
     (_check_dtls if dtls else _check_stream)(h, jobs, got)
     h.close()
+
+
+# ---- 4. out_len against the size functions -------------------------------------------
+def test_out_len_matches_out_size(launch_log):
+    """The kernels' protected-length arithmetic and tlsrec_stream_out_size /
+    tlsrec_dtls_out_size are one function per wire format: every connection's
+    out_len equals out_size() for its slot and input length, and the length
+    of the oracle's output.  Slots of granularity 0 / 16 / 64 over AES-128-GCM,
+    AES-256-GCM, ChaCha20-Poly1305 and one CCM_8 slot; the stream run mixes
+    TLS 1.2 and 1.3, the DTLS run slots without a CID and with a 3-byte one.
+    A CCM key or a CID in the table means the copy path."""
+    from mbedtls_amd import dtls as D
+    from mbedtls_amd import stream as S
+    G128, G256, CH, CCM8 = M.CIPHER_AES_128_GCM, M.CIPHER_AES_256_GCM, M.CIPHER_CHACHA20_POLY1305, \
+        M.CIPHER_AES_128_CCM_8
+    T12, T13 = M.VERSION_TLS1_2, M.VERSION_TLS1_3
+    shape = [(G128, T12, 0), (G256, T13, 16), (CH, T13, 64), (CCM8, T12, 0),
+             (G128, T13, 64), (G256, T12, 16), (CH, T12, 0), (G256, T13, 0)]
+    keys = [prng_bytes(307000 + s, 48) for s in range(8)]
+    edge = _edge_jobs()
+
+    c = B.Conns([(ci, v, k[:M.KEYLEN[ci]], k[32:48], g) for (ci, v, g), k in zip(shape, keys)])
+    jobs = [((i + i // 8) % 8, _bulk(37000 + i, n), 0x0102030405060708 + i, frag, 23) for i, (n, frag) in enumerate(edge)]
+    launch_log.reset()
+    got = c.encrypt(jobs, odd=True)
+    _assert_copy_frame(launch_log, dtls=False)
+    for i, ((slot, pt, ctr, frag, typ), (r, out)) in enumerate(zip(jobs, got)):
+        ci, v, g = shape[slot]
+        st, want, _, _ = O.stream_encrypt(c.ot[slot], pt, typ, ctr.to_bytes(8, "big"), frag or 16384)
+        assert st == 0 and int(r["status"]) == 0, i
+        assert int(r["out_len"]) == S.out_size(v, ci, g, len(pt), frag) == len(want), (i, slot, len(pt), frag)
+    c.close()
+
+    cids = [b"" if s % 2 == 0 else bytes([0xC0 + s, 1, 2]) for s in range(8)]
+    tab = B.Table([(ci, k[:M.KEYLEN[ci]], k[32:48], cid) for (ci, _, _), k, cid in zip(shape, keys, cids)],
+                  gran_of={s: g for s, (_, _, g) in enumerate(shape)})
+    jobs = [((i + i // 8) % 8, _bulk(38000 + i, n), dctr(2 + i % 3, 1000 + 13 * i), frag, 23)
+            for i, (n, frag) in enumerate(edge)]
+    launch_log.reset()
+    got = tab.encrypt(jobs, odd=True)
+    _assert_copy_frame(launch_log, dtls=True)
+    for i, ((slot, pt, c8, frag, typ), (r, out, _, _)) in enumerate(zip(jobs, got)):
+        ci, _, g = shape[slot]
+        st, want, _, _ = O.dtls_encrypt(tab.ot[slot], pt, typ, c8, frag or 16384)
+        assert st == 0 and int(r["status"]) == 0, i
+        assert int(r["out_len"]) == D.out_size(ci, g, len(cids[slot]), len(pt), frag) == len(want), \
+            (i, slot, len(pt), frag)
+    tab.close()

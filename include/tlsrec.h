@@ -26,10 +26,13 @@
  * Semantics and error codes are those of the reference: 0 on success or a
  * negative MBEDTLS_ERR_SSL_* value (include/mbedtls/ssl.h:40-125); the record
  * is transformed in place and its data_offset / data_len / type are updated
- * exactly as the reference updates them.  Only the AEAD suites are supported
+ * exactly as the reference updates them.  Supported: the AEAD suites
  * (AES-128/192/256-GCM, AES-128/192/256-CCM and CCM_8, ChaCha20-Poly1305,
- * ARIA-128/192/256-GCM and -CCM;
- * TLS 1.2 and 1.3, and DTLS 1.2 records with an RFC 9146 connection ID).
+ * ARIA-128/192/256-GCM and -CCM, Camellia-128/192/256-GCM and -CCM;
+ * TLS 1.2 and 1.3, and DTLS 1.2 records with an RFC 9146 connection ID) on
+ * every entry point, and the TLS 1.2 / DTLS 1.2 AES-128/256-CBC suites with
+ * HMAC-SHA1 / -SHA256 / -SHA384, MAC-then-encrypt or encrypt-then-MAC, on the
+ * key table and the batch entry points (tlsrec_keytab_load_cbc below).
  *
  * Every entry point that touches record data runs on the GPU; there is no CPU
  * fallback.  Without a usable HIP device they return
@@ -89,7 +92,19 @@ extern "C" {
 #define TLSREC_CIPHER_CAMELLIA_128_CCM   20
 #define TLSREC_CIPHER_CAMELLIA_192_CCM   21
 #define TLSREC_CIPHER_CAMELLIA_256_CCM   22
-#define TLSREC_CIPHER_MAX                22
+#define TLSREC_CIPHER_MAX                22      /* the last AEAD id */
+/* AES-CBC + HMAC (MBEDTLS_SSL_MODE_CBC / _CBC_ETM); key-table and batch entry
+ * points only, loaded with tlsrec_keytab_load_cbc.  No TLS suite uses
+ * AES-192-CBC. */
+#define TLSREC_CIPHER_AES_128_CBC        23
+#define TLSREC_CIPHER_AES_256_CBC        24
+#define TLSREC_CIPHER_CBC_FIRST          23
+#define TLSREC_CIPHER_CBC_LAST           24
+/* record MACs of the CBC suites (no truncated HMAC, no MD5: the reference has
+ * neither in a suite); maclen 20 / 32 / 48 */
+#define TLSREC_MAC_SHA1                  1
+#define TLSREC_MAC_SHA256                2
+#define TLSREC_MAC_SHA384                3
 
 #define TLSREC_MSG_APPLICATION_DATA  23      /* ssl.h:527 */
 #define TLSREC_MSG_CID               25      /* MBEDTLS_SSL_MSG_CID, ssl.h:528 */
@@ -443,6 +458,83 @@ typedef struct tlsrec_tls12_conn {
  * tlsrec_tls13_keytab_derive) or prf. */
 int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                int prf, const tlsrec_tls12_conn *conns, void *stream);
+
+/* ---- AES-CBC + HMAC slots (TLS 1.2 / DTLS 1.2) ---------------------------
+ * The MBEDTLS_SSL_MODE_CBC and MBEDTLS_SSL_MODE_CBC_ETM branches of
+ * mbedtls_ssl_encrypt_buf / _decrypt_buf (ssl_msg.c:906-968, :1080-1253,
+ * :1435-1702, :1717-1801; transform setup ssl_tls.c:7799-7843) for records
+ * of tlsrec_batch_encrypt / _decrypt, their _sized forms and
+ * tlsrec_host_batch_*: a record naming a CBC slot gets the status,
+ * data_offset, data_len, type and bytes the reference produces under that
+ * transform.  A batch may mix CBC and AEAD slots freely.
+ *
+ * The one divergence -- the explicit IV on encrypt: the reference draws it
+ * with psa_generate_random (ssl_msg.c:1124); the engine has no RNG.  The
+ * caller places the 16-byte IV at in_arena + buf_off + data_offset - 16 (as
+ * the ticket API takes its IV); the engine encrypts under it and writes it to
+ * the same offset of out_arena.  data_offset < 16 gives
+ * TLSREC_ERR_SSL_BUFFER_TOO_SMALL where the reference checks it (:1116).
+ *
+ * Failures: status, data_offset and data_len are the reference's
+ * (INVALID_MAC under encrypt-then-MAC: data_offset unchanged, data_len less
+ * maclen; under MAC-then-encrypt: the values after :1572-1573, :1700 and
+ * :1738).  The bytes of a record whose status is not 0 are unspecified;
+ * nothing outside [buf_off, buf_off + buf_len) is ever written.
+ *
+ * Out of scope: the stream and DTLS framing layers, session tickets and the
+ * single-record server (tlsrec_encrypt_buf / _decrypt_buf) treat a CBC slot
+ * as a slot that was never loaded; ARIA-CBC, Camellia-CBC and the NULL
+ * cipher; batch key derivation (tlsrec_tls12_keytab_derive) for CBC suites.
+ * tlsrec_keytab_load, tlsrec_transform_setup, tlsrec_tls12_split_key_block,
+ * tlsrec_tls12_make_keys, tlsrec_tls12_keytab_derive, tlsrec_tls13_keytab_derive, tlsrec_stream_out_size
+ * and tlsrec_dtls_out_size answer ids 23 and 24 as unknown ciphers. */
+
+/* One direction of one connection, 128 bytes. */
+typedef struct tlsrec_cbc_key_material {
+    uint8_t cipher;          /* TLSREC_CIPHER_AES_128_CBC / _256_CBC */
+    uint8_t tls_minor;       /* 3 (TLS 1.2 / DTLS 1.2) */
+    uint8_t mac;             /* TLSREC_MAC_* */
+    uint8_t etm;             /* 0 = MAC-then-encrypt, 1 = encrypt-then-MAC (RFC 7366) */
+    uint8_t reserved[44];    /* zero */
+    uint8_t key[32];         /* 16 or 32 bytes used */
+    uint8_t mac_key[48];     /* maclen bytes used */
+} tlsrec_cbc_key_material;
+
+/* tlsrec_keytab_load for CBC slots: the same contract (host or device
+ * `keys`; host material is staged in a device buffer of the call's own and
+ * the call waits for the key setup before it frees it, device material is
+ * read once for the checks and the key setup enqueued on `stream`); the GPU expands the AES round keys of both
+ * directions and the HMAC inner / outer midstates.  Unknown cipher or mac:
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE; tls_minor != 3 or etm > 1:
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA.  A slot may be reloaded from AEAD to CBC and
+ * back; tlsrec_keytab_set_cid works on a CBC slot (DTLS 1.2 connection IDs). */
+int tlsrec_keytab_load_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count,
+                           const tlsrec_cbc_key_material *keys, int keys_on_device, void *stream);
+
+/* Host-only: bytes of explicit IV + ciphertext (+ MAC) a record of content_len
+ * bytes becomes (without a connection ID); 0 for unknown ids. */
+uint32_t tlsrec_cbc_record_len(int mac, int etm, uint32_t content_len);
+/* Host-only: transform->minlen, ssl_tls.c:7822-7835; 0 for unknown ids. */
+uint32_t tlsrec_cbc_minlen(int mac, int etm);
+
+/* both directions' material of one connection */
+typedef struct tlsrec_cbc_key_set {
+    tlsrec_cbc_key_material client_write;
+    tlsrec_cbc_key_material server_write;
+} tlsrec_cbc_key_set;
+
+/* Host-only: the mac_key_len != 0 layout of the key block, ssl_tls.c:7858-7886:
+ * client_mac | server_mac | client_key | server_key.  Fills cipher, tls_minor 3,
+ * mac, etm 0 (the caller sets it from the negotiated extension), key and
+ * mac_key; the rest is zero.  A block shorter than 2 * maclen + 2 * key_len is
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA, an unknown cipher or mac
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE. */
+int tlsrec_tls12_split_key_block_cbc(int cipher, int mac, const unsigned char *keyblk, size_t keyblk_len,
+                                     tlsrec_cbc_key_set *out);
+/* PRF(master, "key expansion", randbytes) + the split above (arguments as
+ * tlsrec_tls12_make_keys). */
+int tlsrec_tls12_make_keys_cbc(int prf, int cipher, int mac, const unsigned char master[48],
+                               const unsigned char randbytes[64], tlsrec_cbc_key_set *out);
 
 /* ---- TLS stream record layer --------------------------
  * Whole-connection framing on the device: received byte streams are split at

@@ -24,6 +24,7 @@ from .batch import (KeyTable, batch_decrypt, batch_encrypt, frame_check, host_ba
                     records, results, seq_bytes)
 from .record import Record, Transform, decrypt_buf, encrypt_buf  # noqa: F401
 from .shard import Shard, broadcast_keys, reduce_status, shard_bounds, status_counts  # noqa: F401
+from . import cbc  # noqa: F401
 from . import tls12  # noqa: F401
 from .tls12 import (tls_prf, tls12_compute_master, tls12_split_key_block, tls12_make_keys,  # noqa: F401
                     tls12_export_keying_material, tls12_keytab_derive, tls12_slots)

@@ -51,6 +51,10 @@ CIPHER_CAMELLIA_128_CCM, CIPHER_CAMELLIA_192_CCM, CIPHER_CAMELLIA_256_CCM = 20, 
 KEYLEN = {1: 16, 2: 32, 3: 32, 4: 24, 5: 16, 6: 24, 7: 32, 8: 16, 9: 24, 10: 32, 11: 16, 12: 24, 13: 32,
           14: 16, 15: 24, 16: 32, 17: 16, 18: 24, 19: 32, 20: 16, 21: 24, 22: 32}
 TAGLEN = {c: (8 if 8 <= c <= 10 else 16) for c in KEYLEN}
+# AES-CBC + HMAC (key table and batch entry points only; mbedtls_amd/cbc.py).  Not in
+# KEYLEN / TAGLEN, which list the AEAD ids.
+CIPHER_AES_128_CBC, CIPHER_AES_256_CBC = 23, 24
+MAC_SHA1, MAC_SHA256, MAC_SHA384 = 1, 2, 3
 MSG_APPLICATION_DATA = 23
 MSG_CID = 25
 CID_LEN_MAX = 32
@@ -65,6 +69,9 @@ IS_CLIENT, IS_SERVER = 0, 1                                 # MBEDTLS_SSL_IS_CLI
 KEY_MATERIAL = np.dtype([("cipher", "u1"), ("tls_minor", "u1"), ("fixed_ivlen", "u1"),
                          ("taglen", "u1"), ("granularity", "u1"), ("reserved", "u1", 11),
                          ("iv", "u1", 16), ("key", "u1", 32)])
+CBC_KEY_MATERIAL = np.dtype([("cipher", "u1"), ("tls_minor", "u1"), ("mac", "u1"), ("etm", "u1"),
+                             ("reserved", "u1", 44), ("key", "u1", 32), ("mac_key", "u1", 48)])
+assert CBC_KEY_MATERIAL.itemsize == 128
 BATCH_REC = np.dtype([("buf_off", "<u8"), ("buf_len", "<u4"), ("data_offset", "<u4"),
                       ("data_len", "<u4"), ("slot", "<u4"), ("ctr", "u1", 8), ("type", "u1"),
                       ("ver", "u1", 2), ("cid_len", "u1"), ("cid_off", "<u4")], align=False)
@@ -179,6 +186,11 @@ SIGNATURES = {
     "tlsrec_dtls_decrypt": (_INT, [_VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_dtls_out_size": (ctypes.c_uint64, [_INT, _U32, _U32, ctypes.c_uint64, _U32]),
     "tlsrec_dtls_encrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
+    "tlsrec_keytab_load_cbc": (_INT, [_VP, _U32, _U32, _VP, _INT, _VP]),
+    "tlsrec_cbc_record_len": (_U32, [_INT, _INT, _U32]),
+    "tlsrec_cbc_minlen": (_U32, [_INT, _INT]),
+    "tlsrec_tls12_split_key_block_cbc": (_INT, [_INT, _INT, _VP, _SZ, _VP]),
+    "tlsrec_tls12_make_keys_cbc": (_INT, [_INT, _INT, _INT, _VP, _VP, _VP]),
     "tlsrec_version_string": (ctypes.c_char_p, []),
 }
 
@@ -240,6 +252,7 @@ def test_library():
 # the launch log of the test-hooks build (csrc/tlsrec_internal.h TLSREC_LAUNCH_LOG)
 LOG_GCM, LOG_CHACHA, LOG_ALT_GCM, LOG_CCM, LOG_BUCKET, LOG_SEND_FRAME, LOG_DTLS_RX_FRAME, LOG_STREAM_RX_FRAME = \
     1, 2, 3, 4, 5, 6, 7, 8
+LOG_CBC = 9
 LAUNCH_LOG_ENTRY = np.dtype([("kind", "<i4"), ("p0", "<i4"), ("p1", "<i4"), ("p2", "<i4"), ("p3", "<i4")])
 
 

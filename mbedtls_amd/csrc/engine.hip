@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "tlsrec.h"
+#include "tlsrec_cbc.h"
 #include "tlsrec_frame.h"
 #include "tlsrec_internal.h"
 
@@ -35,6 +36,8 @@ struct tlsrec_keytab {
     uint8_t *h_cipher;        /* host mirror of each slot's cipher */
     uint32_t cipher_mask;     /* 1 << TLSREC_CIPHER_* of every loaded slot */
     uint32_t nloaded;         /* slots holding a key */
+    uint32_t cbc_variants;    /* CBC slots loaded: bit 3 * (cipher - CBC_FIRST) + (mac - 1) (tlsrec__launch_cbc) */
+    uint32_t cbc_etm;         /* ... and bit etm: the MAC orders among them (launch log) */
     volatile uint32_t has_cid; /* some slot was given a DTLS connection ID: launch the CID kernels */
     uint8_t *d_dummy;         /* GcmArgs::dummy: 64 KiB the idle lanes of a wave-pass round load and store */
     HostPipe *pipe;
@@ -59,7 +62,7 @@ extern "C" const char *tlsrec_version_string(void)
 {
     return "tlsrec 0.2 gfx950: aes-128/192/256-gcm(L=4/8/16/64, T-tables in LDS, GHASH 4-bit position tables) "
            "aes-ccm/ccm_8(lane per record) chacha20-poly1305(L=1/2/4/8, 26-bit limbs) "
-           "tls13-key-schedule(hkdf-sha256/384) stream-record-layer aria-128/192/256-gcm/ccm camellia-128/192/256-gcm/ccm dtls1.2-cid dtls1.2-datagram-record-layer(anti-replay) session-tickets";
+           "tls13-key-schedule(hkdf-sha256/384) stream-record-layer aria-128/192/256-gcm/ccm camellia-128/192/256-gcm/ccm dtls1.2-cid dtls1.2-datagram-record-layer(anti-replay) session-tickets aes-128/256-cbc-hmac-sha1/sha256/sha384(mac-then-encrypt, encrypt-then-mac; lane per record)";
 }
 
 extern "C" int tlsrec_keytab_create(tlsrec_keytab **out, uint32_t capacity)
@@ -147,6 +150,18 @@ extern "C" void tlsrec_keytab_free(tlsrec_keytab *kt)
     free(kt);
 }
 
+static const uint32_t CBC_CIPHER_BITS = (1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC);
+
+/* A slot that held a CBC key and now gets an AEAD one: its decryption round
+ * keys (SlotState::ark) and HMAC midstates (the head of its table area) are
+ * not all overwritten by the AEAD key setup, so one kernel zeroizes them,
+ * enqueued before the key setup (a table that never held a CBC key: nothing). */
+static int wipe_cbc_state(tlsrec_keytab *kt, uint32_t first, uint32_t count, hipStream_t st)
+{
+    if (!(kt->cipher_mask & CBC_CIPHER_BITS)) return 0;
+    return hip_ok(tlsrec__launch_cbc_wipe(kt->d_slots, kt->d_ghtab, kt->d_cipher, first, count, st));
+}
+
 static int check_material(const tlsrec_key_material *k)
 {
     if (k->cipher < TLSREC_CIPHER_AES_128_GCM || k->cipher > TLSREC_CIPHER_MAX)
@@ -181,6 +196,10 @@ extern "C" int tlsrec_keytab_load(tlsrec_keytab *kt, uint32_t first, uint32_t co
             return r;
         }
     }
+    if (wipe_cbc_state(kt, first, count, st)) {
+        free(host);
+        return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
     for (uint32_t i = 0; i < count; i++) {
         if (kt->h_cipher[first + i] == 0) kt->nloaded++;
         kt->h_cipher[first + i] = hk[i].cipher;
@@ -198,6 +217,92 @@ extern "C" int tlsrec_keytab_load(tlsrec_keytab *kt, uint32_t first, uint32_t co
     return hip_ok(tlsrec__launch_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, src, first, count, st));
 }
 
+static int check_cbc_material(const tlsrec_cbc_key_material *k)
+{
+    if (cbc_keylen(k->cipher) == 0 || cbc_maclen(k->mac) == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (k->tls_minor != 3 || k->etm > 1) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    return 0;
+}
+
+extern "C" int tlsrec_keytab_load_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count,
+                                      const tlsrec_cbc_key_material *keys, int keys_on_device, void *stream)
+{
+    /* host material is judged first: its errors need neither a table nor a device */
+    if (keys && !keys_on_device)
+        for (uint32_t i = 0; i < count; i++) {
+            const int r = check_cbc_material(&keys[i]);
+            if (r) return r;
+        }
+    if (!kt || !keys || first > kt->capacity || count > kt->capacity - first) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (count == 0) return 0;
+    hipStream_t st = (hipStream_t) stream;
+    const size_t bytes = sizeof(*keys) * (size_t) count;
+    /* the checks read the material on the host; device-resident material is
+     * fetched for them, host material is staged on the device for the kernel */
+    tlsrec_cbc_key_material *host = NULL, *dev = NULL;
+    if (keys_on_device) {
+        host = (tlsrec_cbc_key_material *) malloc(bytes);
+        if (!host) return TLSREC_ERR_SSL_ALLOC_FAILED;
+        if (hipMemcpyAsync(host, keys, bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            free(host);
+            return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+        }
+    }
+    const tlsrec_cbc_key_material *hk = keys_on_device ? host : keys;
+    int r = 0;
+    uint32_t variants = 0, etm = 0;
+    for (uint32_t i = 0; i < count && !r; i++) {
+        r = check_cbc_material(&hk[i]);
+        if (!r) {
+            variants |= 1u << (3 * (hk[i].cipher - TLSREC_CIPHER_CBC_FIRST) + (hk[i].mac - 1));
+            etm |= 1u << hk[i].etm;
+        }
+    }
+    if (!r && !keys_on_device) {
+        if (hipMalloc((void **) &dev, bytes) != hipSuccess) r = TLSREC_ERR_SSL_ALLOC_FAILED;
+        else if (hipMemcpyAsync(dev, keys, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                 hipStreamSynchronize(st) != hipSuccess)
+            r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
+    if (!r) {
+        for (uint32_t i = 0; i < count; i++) {
+            if (kt->h_cipher[first + i] == 0) kt->nloaded++;
+            kt->h_cipher[first + i] = hk[i].cipher;
+            kt->cipher_mask |= 1u << hk[i].cipher;
+        }
+        kt->cbc_variants |= variants;
+        kt->cbc_etm |= etm;
+        r = hip_ok(tlsrec__launch_cbc_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, dev ? dev : keys, first, count,
+                                               st));
+    }
+    if (host) {
+        memset(host, 0, bytes);
+        free(host);
+    }
+    if (dev) {
+        /* the staged copy holds raw keys: wait for the kernel, zeroize, free */
+        hipStreamSynchronize(st);
+        hipMemset(dev, 0, bytes);
+        hipFree(dev);
+    }
+    return r;
+}
+
+extern "C" uint32_t tlsrec_cbc_record_len(int mac, int etm, uint32_t content_len)
+{
+    return cbc_record_len(mac, etm, content_len);
+}
+
+extern "C" uint32_t tlsrec_cbc_minlen(int mac, int etm)
+{
+    const uint32_t ml = cbc_maclen(mac);
+    if (ml == 0 || etm < 0 || etm > 1) return 0;
+    /* ssl_tls.c:7822-7835: one block plus MAC, or the first multiple of the
+     * block length above maclen; plus the explicit IV */
+    return (etm ? ml + 16 : ml + 16 - ml % 16) + 16;
+}
+
 /* Device-side producers of key material (keysched.hip) write into the
  * table's staging area and then commit: bookkeeping as tlsrec_keytab_load,
  * then the key-setup kernel on the staged slots. */
@@ -208,6 +313,7 @@ extern "C" const uint4 *tlsrec__keytab_ghtab(const tlsrec_keytab *kt) { return k
 extern "C" int tlsrec__keytab_commit_staged(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                             hipStream_t st)
 {
+    if (wipe_cbc_state(kt, first, count, st)) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     for (uint32_t i = 0; i < count; i++) {
         if (kt->h_cipher[first + i] == 0) kt->nloaded++;
         kt->h_cipher[first + i] = (uint8_t) cipher;
@@ -565,7 +671,9 @@ static int bucket(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_
 {
     /* AES-128-GCM, AES-256-GCM, AES-192-GCM, AES-CCM slots, ChaCha, ARIA-128/192/256-GCM,
      * Camellia-128/192/256-GCM slots, end */
-    const size_t nk = 10 * (size_t) kt->capacity + CP_SPREAD + 1;
+    /* ... and, only while the table holds one, the AES-CBC class */
+    const uint32_t cbc_mask = (1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC);
+    const size_t nk = ((kt->cipher_mask & cbc_mask) ? 11 : 10) * (size_t) kt->capacity + CP_SPREAD + 1;
     b.scan_bytes = tlsrec__scan_scratch_bytes((uint32_t) nk);
     const size_t al = 256;
     const size_t szk = (nk * 4 + al - 1) / al * al, szp = ((size_t) n * 4 + al - 1) / al * al;
@@ -697,6 +805,8 @@ struct BatchOpt {
     bool grouped = false;                /* a key's records are contiguous (the stream / DTLS layers: a connection's
                                             records in order): no bucket pass, the kernels walk them in place */
     const uint64_t *src_off = nullptr;   /* encrypt: contents at in + src_off[i] (tlsrec__batch_src) */
+    bool no_cbc = false;                 /* the stream / DTLS layers: a CBC slot counts as never loaded
+                                            (no CBC kernel; its records get the bad-slot result) */
 };
 
 static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res, uint32_t n,
@@ -708,7 +818,8 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
     const int cu = kt->cu;
     const uint32_t avg_bytes = opt.avg_bytes;
     const bool prefilled = opt.prefilled;
-    const uint32_t cmask = opt.only_mask ? (kt->cipher_mask & opt.only_mask) : kt->cipher_mask;
+    const uint32_t cmask = (opt.only_mask ? (kt->cipher_mask & opt.only_mask) : kt->cipher_mask) &
+                           (opt.no_cbc ? ~CBC_CIPHER_BITS : ~0u);
     const uint32_t skip = g_test_skip;
     /* A table holding a single key, or a batch of one record, needs no
      * grouping: the kernels walk the descriptors in order and flag records
@@ -945,6 +1056,28 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
         TLSREC_LAUNCH_LOG(TLSREC_LOG_CCM, ccm_nr, 0, 0, 0);
         if (tlsrec__launch_ccm(&a, dec, ccm_nr, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
+    /* AES-CBC + HMAC: one launch per (key size, MAC) the table holds, over
+     * bucket class 10 cap + CP_SPREAD */
+    if (!rc && (cmask & ((1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC)))) {
+        uint32_t variants = kt->cbc_variants;
+        if (!(cmask & (1u << TLSREC_CIPHER_AES_128_CBC))) variants &= ~7u;
+        if (!(cmask & (1u << TLSREC_CIPHER_AES_256_CBC))) variants &= 7u;
+        CbcArgs a;
+        a.slots = kt->d_slots;
+        a.ghtab = kt->d_ghtab;
+        a.recs = recs;
+        a.res = res;
+        a.n = n;
+        a.perm = identity ? nullptr : bs.perm;
+        a.lo = identity ? nullptr : bs.offs + 10 * (size_t) cap + CP_SPREAD;
+        a.hi = identity ? nullptr : bs.offs + 11 * (size_t) cap + CP_SPREAD;
+        a.in = in;
+        a.out = out;
+        a.capacity = cap;
+        a.skip = skip;
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC, dec, ((variants | (variants >> 3)) & 7u) << 1, kt->cbc_etm, 0);
+        if (tlsrec__launch_cbc(&a, dec, variants, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
     if (!rc && (cmask & (1u << TLSREC_CIPHER_CHACHA20_POLY1305))) {
         /* 2 lanes per record, more when the batch would not fill the chip
          * (cu x 8 resident waves: 2 per SIMD) */
@@ -971,6 +1104,21 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
         uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
         TLSREC_LAUNCH_LOG(TLSREC_LOG_CHACHA, L, a.src_off != nullptr, 0, 0);
         if (tlsrec__launch_chachapoly(&a, dec, L, grid, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
+    if (!rc && opt.no_cbc && (kt->cipher_mask & CBC_CIPHER_BITS)) {
+        CbcArgs a;
+        a.slots = kt->d_slots;
+        a.ghtab = kt->d_ghtab;
+        a.recs = recs;
+        a.res = res;
+        a.n = n;
+        a.perm = nullptr;
+        a.lo = a.hi = nullptr;
+        a.in = in;
+        a.out = out;
+        a.capacity = kt->capacity;
+        a.skip = skip;
+        if (tlsrec__launch_cbc_refuse(&a, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     tlsrec__scratch_release(&bs.lease);
     return rc;
@@ -1024,6 +1172,7 @@ extern "C" int tlsrec__batch_src(const tlsrec_keytab *kt, const tlsrec_batch_rec
     o.avg_bytes = avg_bytes;
     o.src_off = src_off;
     o.grouped = true;                    /* (the stream / DTLS send paths' records, connection by connection) */
+    o.no_cbc = true;
     return batch(kt, recs, res, n, in_arena, out_arena, 0, stream, 0, o);
 }
 
@@ -1034,6 +1183,7 @@ extern "C" int tlsrec__batch_sized(const tlsrec_keytab *kt, const tlsrec_batch_r
     BatchOpt o;
     o.avg_bytes = avg_bytes;
     o.grouped = true;                    /* (the stream / DTLS layers' records, connection by connection) */
+    o.no_cbc = true;
     o.prefilled = prefilled != 0;
     return batch(kt, recs, res, n, in_arena, out_arena, 0, stream, dec, o);
 }

@@ -422,6 +422,8 @@ __device__ __forceinline__ uint32_t bucket_key(const BucketArgs &a, const tlsrec
         case TLSREC_CIPHER_CAMELLIA_192_GCM: return 8 * a.capacity + S + slot;
         case TLSREC_CIPHER_CAMELLIA_256_GCM: return 9 * a.capacity + S + slot;
         default:
+            /* AES-CBC + HMAC (cbc.hip): the class after Camellia-GCM, 10 cap + S + slot */
+            if (c >= TLSREC_CIPHER_CBC_FIRST && c <= TLSREC_CIPHER_CBC_LAST) return 10 * a.capacity + S + slot;
             return (tlsrec_cipher_is_ccm(c) || tlsrec_cipher_is_alt_ccm(c)) ? 3 * a.capacity + slot : 0xffffffffu;
     }
 }
@@ -521,7 +523,8 @@ __global__ __launch_bounds__(256) void tlsrec_bucket_scatter_kernel(BucketArgs a
         a.perm[p] = i;
         /* the GCM classes' descriptors in perm order (not CCM, 3 cap.., or
          * ChaCha, 4 cap..4 cap + CP_SPREAD: their kernels read recs[]) */
-        if (a.srecs && (kr.x < 3 * a.capacity || kr.x >= 4 * a.capacity + CP_SPREAD)) a.srecs[p] = a.recs[i];
+        if (a.srecs && (kr.x < 3 * a.capacity || (kr.x >= 4 * a.capacity + CP_SPREAD && kr.x < 10 * a.capacity + CP_SPREAD)))
+            a.srecs[p] = a.recs[i];     /* (nor CBC, 10 cap + CP_SPREAD..) */
     }
 }
 

@@ -1201,6 +1201,53 @@ extern "C" int tlsrec_tls12_make_keys(int prf, int cipher, const unsigned char m
     return r;
 }
 
+/* the CBC + HMAC suites' layout (mac_key_len != 0), ssl_tls.c:7858-7886:
+ * client_mac | server_mac | client_key | server_key (TLS 1.2 carries the CBC
+ * IV in each record, so the IV part of the block goes unused) */
+static size_t cbc_split_keylen(int cipher)
+{
+    return cipher == TLSREC_CIPHER_AES_128_CBC ? 16 : cipher == TLSREC_CIPHER_AES_256_CBC ? 32 : 0;
+}
+static size_t cbc_split_maclen(int mac)
+{
+    return mac == TLSREC_MAC_SHA1 ? 20 : mac == TLSREC_MAC_SHA256 ? 32 : mac == TLSREC_MAC_SHA384 ? 48 : 0;
+}
+
+extern "C" int tlsrec_tls12_split_key_block_cbc(int cipher, int mac, const unsigned char *keyblk, size_t keyblk_len,
+                                                tlsrec_cbc_key_set *out)
+{
+    if (!out || !keyblk) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
+    if (kl == 0 || ml == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (keyblk_len < 2 * ml + 2 * kl) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    memset(out, 0, sizeof(*out));
+    tlsrec_cbc_key_material *dir[2] = { &out->client_write, &out->server_write };
+    for (int i = 0; i < 2; i++) {
+        dir[i]->cipher = (uint8_t) cipher;
+        dir[i]->tls_minor = 3;
+        dir[i]->mac = (uint8_t) mac;
+        memcpy(dir[i]->mac_key, keyblk + i * ml, ml);
+        memcpy(dir[i]->key, keyblk + 2 * ml + i * kl, kl);
+    }
+    return 0;
+}
+
+extern "C" int tlsrec_tls12_make_keys_cbc(int prf, int cipher, int mac, const unsigned char master[48],
+                                          const unsigned char randbytes[64], tlsrec_cbc_key_set *out)
+{
+    const int a = prf_index(prf);
+    if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
+    if (kl == 0 || ml == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (!master || !randbytes || !out) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    unsigned char keyblk[160];
+    const size_t need = 2 * ml + 2 * kl;
+    int r = prf_run(a, master, 48, "key expansion", 13, randbytes, 64, nullptr, 0, keyblk, need);
+    if (r == 0) r = tlsrec_tls12_split_key_block_cbc(cipher, mac, keyblk, need, out);
+    wipe(keyblk, sizeof(keyblk));
+    return r;
+}
+
 extern "C" int tlsrec_tls12_export_keying_material(int prf, const unsigned char master[48],
                                                    const unsigned char randbytes[64], const char *label,
                                                    size_t label_len, const unsigned char *context,

@@ -87,7 +87,7 @@ __device__ __forceinline__ uint32_t slot_minor(const SlotState *slots, uint32_t 
 {
     if (slot >= cap) return 0;
     const tlsrec_key_material &k = slots[slot].km;
-    return k.cipher ? k.tls_minor : 0;
+    return (k.cipher && k.cipher <= TLSREC_CIPHER_MAX) ? k.tls_minor : 0;   /* (a CBC slot: as never loaded) */
 }
 
 /* add v to the batch's byte count: a wave-wide sum, one atomic per wave, on
@@ -595,7 +595,7 @@ __device__ __forceinline__ OutShape out_shape(const SlotState *slots, uint32_t c
     OutShape o = { 0, 0, 0, 16, 16 };
     if (slot >= cap) return o;
     const tlsrec_key_material &k = slots[slot].km;
-    if (!k.cipher) return o;
+    if (!k.cipher || k.cipher > TLSREC_CIPHER_MAX) return o;   /* (a CBC slot: as never loaded) */
     o.ok = 1;
     o.tls13 = k.tls_minor == 4;
     o.head = (!o.tls13 && k.fixed_ivlen == 4) ? 8u : 0u;

@@ -69,6 +69,8 @@ static_assert(sizeof(SlotState) == 1024, "SlotState layout");
 static_assert(sizeof(tlsrec_key_material) == 64, "key material layout");
 static_assert(sizeof(tlsrec_batch_rec) == 40, "batch record layout");
 static_assert(sizeof(tlsrec_batch_res) == 16, "batch result layout");
+static_assert(sizeof(tlsrec_cbc_key_material) == 128, "CBC key material layout");
+static_assert(sizeof(tlsrec_cbc_key_set) == 256, "CBC key set layout");
 
 /* Records a kernel processes: positions [*lo, *hi) of `perm` (record
  * indices grouped by key, built by the bucket pass), or, with perm == NULL,
@@ -132,7 +134,7 @@ struct BucketArgs {
     tlsrec_batch_res *res;
     uint32_t n;
     uint32_t capacity;
-    uint32_t *counts;         /* [nk = 10 * capacity + CP_SPREAD + 1] records per (class, slot) */
+    uint32_t *counts;         /* [nk = 10 * capacity + CP_SPREAD + 1, one more class with CBC slots] records per (class, slot) */
     const uint32_t *offs;     /* [nk] their exclusive prefix sums (class start in perm) */
     uint2 *keyrank;           /* [n] each record's (key, rank within its key) from the count pass */
     uint32_t nk;
@@ -156,9 +158,34 @@ struct CcmArgs {
     uint32_t skip;            /* test hook, as GcmArgs::skip */
 };
 
+/* AES-CBC + HMAC records (cbc.hip): one lane per record, key passes per wave.
+ * The bucket pass puts them in their own class, after the Camellia-GCM ones:
+ * keys [10 cap + CP_SPREAD, 11 cap + CP_SPREAD), counted only while the table
+ * holds a CBC slot. */
+struct CbcArgs {
+    const SlotState *slots;
+    const uint4 *ghtab;       /* the slots' HMAC midstates (tlsrec_cbc.h) */
+    const tlsrec_batch_rec *recs;
+    tlsrec_batch_res *res;
+    uint64_t n;
+    const uint32_t *perm;
+    const uint32_t *lo, *hi;
+    const uint8_t *in;
+    uint8_t *out;
+    uint32_t capacity;
+    uint32_t skip;            /* test hook, as GcmArgs::skip */
+};
+
 } /* namespace tlsrec */
 
 extern "C" {
+hipError_t tlsrec__launch_cbc(const tlsrec::CbcArgs *a, int dec, uint32_t variants, hipStream_t st);
+hipError_t tlsrec__launch_cbc_refuse(const tlsrec::CbcArgs *a, hipStream_t st);
+hipError_t tlsrec__launch_cbc_wipe(tlsrec::SlotState *slots, uint4 *ghtab, const uint8_t *cipher_of, uint32_t first,
+                                   uint32_t count, hipStream_t st);
+hipError_t tlsrec__launch_cbc_keysetup(tlsrec::SlotState *slots, uint4 *ghtab, uint8_t *cipher_of,
+                                       const tlsrec_cbc_key_material *keys, uint32_t first, uint32_t count,
+                                       hipStream_t st);
 hipError_t tlsrec__launch_ccm(const tlsrec::CcmArgs *a, int dec, uint32_t nr_mask, hipStream_t st);
 hipError_t tlsrec__launch_keysetup(tlsrec::SlotState *slots, uint4 *ghtab, uint8_t *cipher_of,
                                    const tlsrec_key_material *keys,
@@ -221,6 +248,8 @@ hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream
  *                   workgroup), p2 GcmArgs::tm, p3 src_off set
  *   CHACHA          p0 lanes per record, p1 src_off set
  *   ALT_GCM / CCM   p0 the cipher / the nr mask
+ *   CBC             p0 direction (1 = decrypt), p1 mask of MACs (1 << TLSREC_MAC_*),
+ *                   p2 mask of etm values (1 << etm) of the table's CBC slots
  *   BUCKET          p0 1 = bucket pass taken, 0 = identity order
  *   SEND_FRAME      p0 1 = out_frame_conn_kernel<W> (contents read in place),
  *                   0 = map + send_frame_kernel<W, 64> (copied); p1 1 = DTLS
@@ -237,7 +266,8 @@ enum {
     TLSREC_LOG_BUCKET = 5,
     TLSREC_LOG_SEND_FRAME = 6,
     TLSREC_LOG_DTLS_RX_FRAME = 7,
-    TLSREC_LOG_STREAM_RX_FRAME = 8
+    TLSREC_LOG_STREAM_RX_FRAME = 8,
+    TLSREC_LOG_CBC = 9
 };
 #ifdef TLSREC_TEST_HOOKS
 extern "C" void tlsrec__test_launch_log_add(int32_t kind, int32_t p0, int32_t p1, int32_t p2, int32_t p3);

@@ -32,7 +32,8 @@
  * TLS 1.2 and 1.3, and DTLS 1.2 records with an RFC 9146 connection ID) on
  * every entry point, and the TLS 1.2 / DTLS 1.2 AES-128/256-CBC suites with
  * HMAC-SHA1 / -SHA256 / -SHA384, MAC-then-encrypt or encrypt-then-MAC, on the
- * key table and the batch entry points (tlsrec_keytab_load_cbc below).
+ * key table, the batch entry points (tlsrec_keytab_load_cbc below) and the
+ * _ex forms of the stream and DTLS calls (tlsrec_frame_opts below).
  *
  * Every entry point that touches record data runs on the GPU; there is no CPU
  * fallback.  Without a usable HIP device they return
@@ -93,8 +94,8 @@ extern "C" {
 #define TLSREC_CIPHER_CAMELLIA_192_CCM   21
 #define TLSREC_CIPHER_CAMELLIA_256_CCM   22
 #define TLSREC_CIPHER_MAX                22      /* the last AEAD id */
-/* AES-CBC + HMAC (MBEDTLS_SSL_MODE_CBC / _CBC_ETM); key-table and batch entry
- * points only, loaded with tlsrec_keytab_load_cbc.  No TLS suite uses
+/* AES-CBC + HMAC (MBEDTLS_SSL_MODE_CBC / _CBC_ETM); key table, batch entry
+ * points and the _ex framing calls, loaded with tlsrec_keytab_load_cbc.  No TLS suite uses
  * AES-192-CBC. */
 #define TLSREC_CIPHER_AES_128_CBC        23
 #define TLSREC_CIPHER_AES_256_CBC        24
@@ -481,9 +482,14 @@ int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count
  * :1738).  The bytes of a record whose status is not 0 are unspecified;
  * nothing outside [buf_off, buf_off + buf_len) is ever written.
  *
- * Out of scope: the stream and DTLS framing layers, session tickets and the
- * single-record server (tlsrec_encrypt_buf / _decrypt_buf) treat a CBC slot
- * as a slot that was never loaded; ARIA-CBC, Camellia-CBC and the NULL
+ * The stream and DTLS framing layers take CBC slots through their _ex entry
+ * points with TLSREC_FRAME_CBC set (tlsrec_frame_opts below); the plain
+ * tlsrec_stream_* / tlsrec_dtls_* calls treat a CBC slot as a slot that was
+ * never loaded.
+ *
+ * Out of scope: session tickets and the single-record server
+ * (tlsrec_encrypt_buf / _decrypt_buf) treat a CBC slot as a slot that was
+ * never loaded; ARIA-CBC, Camellia-CBC and the NULL
  * cipher; batch key derivation (tlsrec_tls12_keytab_derive) for CBC suites.
  * tlsrec_keytab_load, tlsrec_transform_setup, tlsrec_tls12_split_key_block,
  * tlsrec_tls12_make_keys, tlsrec_tls12_keytab_derive, tlsrec_tls13_keytab_derive, tlsrec_stream_out_size
@@ -727,6 +733,63 @@ int tlsrec_dtls_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_out *stream
                         const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
                         tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
                         uint32_t *nrecords, void *stream);
+
+/* ---- AES-CBC + HMAC connections in the stream and DTLS layers -------------
+ * The four framing calls above with one more argument.  opts == NULL is the
+ * plain call, byte for byte.  With TLSREC_FRAME_CBC a connection whose slot
+ * holds a CBC key (tlsrec_keytab_load_cbc) is framed, protected and finished
+ * as the reference does under that transform; every AEAD connection of the
+ * call gets the results and bytes the plain call gives it.
+ *
+ * Limits follow the slot's kind.  An AEAD slot keeps TLSREC_MAX_IN_RECORD,
+ * TLSREC_OUT_BUF_SPACE, TLSREC_DTLS_MAX_DATAGRAM and
+ * TLSREC_DTLS_OUT_BUFFER_LEN, the AEAD-only build's values.  A CBC slot takes
+ * those of a build with CBC and SHA-384 HMAC suites on (ssl_misc.h:283-301:
+ * MBEDTLS_SSL_MAC_ADD 48, MBEDTLS_SSL_PADDING_ADD 256; :309-319 payload
+ * overhead 16 + 48 + 256 (+ 16 with connection IDs); :382-400 buffer lengths):
+ *   TLS:  13 + 320 + 16384 = 16717; less the 8-byte in_hdr offset, less the
+ *         13 bytes before out_iv;
+ *   DTLS: 13 + 336 + 16384 + 32 = 16765, in and out.
+ *
+ * Send, the explicit IV: the engine has no RNG (see the CBC section above).
+ * Record recs[j] of a CBC connection takes cbc_ivs[16 j .. 16 j + 16); the
+ * frame kernel places it at out_arena + recs[j].buf_off, where it becomes the
+ * first 16 body bytes on the wire.  AEAD records ignore the array.  An
+ * encrypt call with TLSREC_FRAME_CBC and cbc_ivs == NULL, unknown flag bits
+ * or reserved != 0 returns TLSREC_ERR_SSL_BAD_INPUT_DATA before anything is
+ * launched.  The decrypt calls do not read cbc_ivs. */
+#define TLSREC_FRAME_CBC 1u
+#define TLSREC_MAX_IN_RECORD_CBC        16709
+#define TLSREC_OUT_BUF_SPACE_CBC        16704
+#define TLSREC_DTLS_MAX_DATAGRAM_CBC    16765
+#define TLSREC_DTLS_OUT_BUFFER_LEN_CBC  16765
+
+typedef struct tlsrec_frame_opts {
+    uint32_t flags;           /* TLSREC_FRAME_CBC: CBC slots are usable */
+    uint32_t reserved;        /* zero */
+    const uint8_t *cbc_ivs;   /* send only: device, 16 * max_records bytes */
+} tlsrec_frame_opts;
+
+int tlsrec_stream_decrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_in *streams, uint32_t nstreams,
+                             uint8_t *arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
+                             uint32_t max_records, tlsrec_stream_in_res *sres, uint32_t *nrecords,
+                             void *stream, const tlsrec_frame_opts *opts);
+int tlsrec_stream_encrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                             const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
+                             tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
+                             uint32_t *nrecords, void *stream, const tlsrec_frame_opts *opts);
+int tlsrec_dtls_decrypt_ex(const tlsrec_keytab *kt, const tlsrec_dtls_in *conns, uint32_t nconns,
+                           const tlsrec_dgram *dgrams, uint32_t ndgrams, uint8_t *arena, tlsrec_batch_rec *recs,
+                           tlsrec_batch_res *res, int32_t *disp, uint32_t max_records, tlsrec_dtls_in_res *cres,
+                           uint32_t *nrecords, void *stream, const tlsrec_frame_opts *opts);
+int tlsrec_dtls_encrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                           const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
+                           tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
+                           uint32_t *nrecords, void *stream, const tlsrec_frame_opts *opts);
+/* tlsrec_stream_out_size / tlsrec_dtls_out_size for a CBC slot (mac:
+ * TLSREC_MAC_*, etm: 0 / 1); 0 for unknown ids or cid_len > TLSREC_CID_LEN_MAX. */
+uint64_t tlsrec_stream_out_size_cbc(int mac, int etm, uint64_t in_len, uint32_t max_frag);
+uint64_t tlsrec_dtls_out_size_cbc(int mac, int etm, uint32_t cid_len, uint64_t in_len, uint32_t max_frag);
 
 /* ---- session tickets (library/ssl_ticket.c) ------------
  * mbedtls_ssl_ticket_write / mbedtls_ssl_ticket_parse for a batch of tickets

@@ -35,6 +35,10 @@ DTLS_DROPPED, DTLS_NOT_REACHED = 1, 2
 DTLS_ANTI_REPLAY, DTLS_IGNORE_UNEXPECTED_CID = 1, 2
 MAX_IN_RECORD = 16421
 OUT_BUF_SPACE = 16416
+# a CBC slot's limits (the _ex framing calls with FRAME_CBC: the limit follows the slot's kind)
+MAX_IN_RECORD_CBC, OUT_BUF_SPACE_CBC = 16709, 16704
+DTLS_MAX_DATAGRAM_CBC = DTLS_OUT_BUFFER_LEN_CBC = 16765
+FRAME_CBC = 1
 
 VERSION_TLS1_2 = 0x0303
 VERSION_TLS1_3 = 0x0304
@@ -51,8 +55,8 @@ CIPHER_CAMELLIA_128_CCM, CIPHER_CAMELLIA_192_CCM, CIPHER_CAMELLIA_256_CCM = 20, 
 KEYLEN = {1: 16, 2: 32, 3: 32, 4: 24, 5: 16, 6: 24, 7: 32, 8: 16, 9: 24, 10: 32, 11: 16, 12: 24, 13: 32,
           14: 16, 15: 24, 16: 32, 17: 16, 18: 24, 19: 32, 20: 16, 21: 24, 22: 32}
 TAGLEN = {c: (8 if 8 <= c <= 10 else 16) for c in KEYLEN}
-# AES-CBC + HMAC (key table and batch entry points only; mbedtls_amd/cbc.py).  Not in
-# KEYLEN / TAGLEN, which list the AEAD ids.
+# AES-CBC + HMAC (key table, batch entry points and the _ex framing calls; mbedtls_amd/cbc.py).
+# Not in KEYLEN / TAGLEN, which list the AEAD ids.
 CIPHER_AES_128_CBC, CIPHER_AES_256_CBC = 23, 24
 MAC_SHA1, MAC_SHA256, MAC_SHA384 = 1, 2, 3
 MSG_APPLICATION_DATA = 23
@@ -115,6 +119,11 @@ class CTransform(ctypes.Structure):
                 ("granularity", ctypes.c_uint32), ("in_cid_len", ctypes.c_uint8),
                 ("out_cid_len", ctypes.c_uint8), ("in_cid", ctypes.c_ubyte * 32),
                 ("out_cid", ctypes.c_ubyte * 32)]
+
+
+class CFrameOpts(ctypes.Structure):
+    """tlsrec_frame_opts: the options of the tlsrec_stream_*_ex / tlsrec_dtls_*_ex calls"""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("cbc_ivs", ctypes.c_void_p)]
 
 
 class CKeySet(ctypes.Structure):
@@ -186,6 +195,12 @@ SIGNATURES = {
     "tlsrec_dtls_decrypt": (_INT, [_VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_dtls_out_size": (ctypes.c_uint64, [_INT, _U32, _U32, ctypes.c_uint64, _U32]),
     "tlsrec_dtls_encrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
+    "tlsrec_stream_decrypt_ex": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "tlsrec_stream_encrypt_ex": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "tlsrec_dtls_decrypt_ex": (_INT, [_VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "tlsrec_dtls_encrypt_ex": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "tlsrec_stream_out_size_cbc": (ctypes.c_uint64, [_INT, _INT, ctypes.c_uint64, _U32]),
+    "tlsrec_dtls_out_size_cbc": (ctypes.c_uint64, [_INT, _INT, _U32, ctypes.c_uint64, _U32]),
     "tlsrec_keytab_load_cbc": (_INT, [_VP, _U32, _U32, _VP, _INT, _VP]),
     "tlsrec_cbc_record_len": (_U32, [_INT, _INT, _U32]),
     "tlsrec_cbc_minlen": (_U32, [_INT, _INT]),

@@ -805,8 +805,8 @@ struct BatchOpt {
     bool grouped = false;                /* a key's records are contiguous (the stream / DTLS layers: a connection's
                                             records in order): no bucket pass, the kernels walk them in place */
     const uint64_t *src_off = nullptr;   /* encrypt: contents at in + src_off[i] (tlsrec__batch_src) */
-    bool no_cbc = false;                 /* the stream / DTLS layers: a CBC slot counts as never loaded
-                                            (no CBC kernel; its records get the bad-slot result) */
+    bool no_cbc = false;                 /* the stream / DTLS layers without TLSREC_FRAME_CBC: a CBC slot counts as
+                                            never loaded (no CBC kernel; its records get the bad-slot result) */
 };
 
 static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res, uint32_t n,
@@ -1163,6 +1163,11 @@ extern "C" int tlsrec__keytab_src_ok(const tlsrec_keytab *kt)
     return kt && !kt->has_cid && (kt->cipher_mask & ~ok) == 0;   /* (the CID kernel variants read in place) */
 }
 
+extern "C" int tlsrec__keytab_has_cbc(const tlsrec_keytab *kt)
+{
+    return kt && (kt->cipher_mask & CBC_CIPHER_BITS) != 0;
+}
+
 extern "C" int tlsrec__batch_src(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res,
                                  uint32_t n, const uint8_t *in_arena, uint8_t *out_arena, void *stream,
                                  uint32_t avg_bytes, const uint64_t *src_off)
@@ -1178,12 +1183,12 @@ extern "C" int tlsrec__batch_src(const tlsrec_keytab *kt, const tlsrec_batch_rec
 
 extern "C" int tlsrec__batch_sized(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res,
                                    uint32_t n, const uint8_t *in_arena, uint8_t *out_arena, void *stream, int dec,
-                                   uint32_t avg_bytes, int prefilled)
+                                   uint32_t avg_bytes, int prefilled, int cbc)
 {
     BatchOpt o;
     o.avg_bytes = avg_bytes;
     o.grouped = true;                    /* (the stream / DTLS layers' records, connection by connection) */
-    o.no_cbc = true;
+    o.no_cbc = cbc == 0;                 /* (cbc: the _ex calls with TLSREC_FRAME_CBC) */
     o.prefilled = prefilled != 0;
     return batch(kt, recs, res, n, in_arena, out_arena, 0, stream, dec, o);
 }

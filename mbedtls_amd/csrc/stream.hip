@@ -31,10 +31,14 @@
 #include <type_traits>
 
 #include "tlsrec.h"
+#include "tlsrec_cbc.h"
 #include "tlsrec_frame.h"
 #include "tlsrec_internal.h"
 
 using tlsrec::SlotState;
+using tlsrec::cbc_body_len;
+using tlsrec::cbc_is_cipher;
+using tlsrec::cbc_maclen;
 
 /* engine.hip */
 extern "C" const SlotState *tlsrec__keytab_slots(const tlsrec_keytab *kt);
@@ -82,12 +86,34 @@ __device__ __forceinline__ void guard_result(tlsrec_batch_res *res)
     *res = r;
 }
 
+/* Every kernel below that looks at a connection's slot is a template on CBC:
+ * false is the plain calls' kernel (a CBC slot: as never loaded; the AEAD-only
+ * build's limits as constants), true the _ex calls' with TLSREC_FRAME_CBC,
+ * launched only while the table holds a CBC slot -- so the AEAD-only kernels
+ * carry no branch for it. */
+
 /* TLS minor version of a loaded slot (3 or 4), 0 if the slot is unusable */
+template <bool CBC = false>
 __device__ __forceinline__ uint32_t slot_minor(const SlotState *slots, uint32_t cap, uint32_t slot)
 {
     if (slot >= cap) return 0;
     const tlsrec_key_material &k = slots[slot].km;
-    return (k.cipher && k.cipher <= TLSREC_CIPHER_MAX) ? k.tls_minor : 0;   /* (a CBC slot: as never loaded) */
+    if (CBC && cbc_is_cipher(k.cipher)) return k.tls_minor;
+    return (k.cipher && k.cipher <= TLSREC_CIPHER_MAX) ? k.tls_minor : 0;   /* (!CBC, a CBC slot: as never loaded) */
+}
+
+/* lim / lim_cbc by the slot's kind (the limits follow it, tlsrec.h) */
+template <bool CBC>
+__device__ __forceinline__ uint32_t slot_limit(const SlotState *slots, uint32_t cap, uint32_t slot, uint32_t lim,
+                                               uint32_t lim_cbc)
+{
+    if constexpr (CBC) return (slot < cap && cbc_is_cipher(slots[slot].km.cipher)) ? lim_cbc : lim;
+    else return lim;
+}
+template <bool CBC>
+__device__ __forceinline__ uint32_t rx_limit(const SlotState *slots, uint32_t cap, uint32_t slot)
+{
+    return slot_limit<CBC>(slots, cap, slot, TLSREC_MAX_IN_RECORD, TLSREC_MAX_IN_RECORD_CBC);
 }
 
 /* add v to the batch's byte count: a wave-wide sum, one atomic per wave, on
@@ -116,9 +142,10 @@ struct HdrStop {
 };
 
 /* Walk one connection's headers (ssl_parse_record_header + fetch_input);
- * f(k, pos, type, ver, dlen) for each complete record. */
+ * f(k, pos, type, ver, dlen) for each complete record; lim = the header + body
+ * limit of the connection's slot kind (rx_limit). */
 template <typename F>
-__device__ HdrStop walk_in(const uint8_t *base, uint32_t len, F f)
+__device__ HdrStop walk_in(const uint8_t *base, uint32_t len, uint32_t lim, F f)
 {
     uint32_t pos = 0, k = 0;
     HdrStop st = { 0, 0 };
@@ -128,7 +155,7 @@ __device__ HdrStop walk_in(const uint8_t *base, uint32_t len, F f)
         if (type < 20 || type > 23) { st.status = TLSREC_ERR_SSL_INVALID_RECORD; break; }   /* :3529-3539 */
         if (ver > (uint32_t) MAX_VERSION) { st.status = TLSREC_ERR_SSL_INVALID_RECORD; break; }
         if (dlen == 0) { st.status = TLSREC_ERR_SSL_INVALID_RECORD; break; }                /* :3723-3726 */
-        if (5 + dlen > TLSREC_MAX_IN_RECORD) { st.status = TLSREC_ERR_SSL_BAD_INPUT_DATA; break; }
+        if (5 + dlen > lim) { st.status = TLSREC_ERR_SSL_BAD_INPUT_DATA; break; }
         if (len - pos < 5 + dlen) break;                                                     /* wait */
         f(k, pos, type, h[1], h[2], dlen);
         k++;
@@ -138,14 +165,15 @@ __device__ HdrStop walk_in(const uint8_t *base, uint32_t len, F f)
     return st;
 }
 
-__global__ void in_count_kernel(const tlsrec_stream_in *s, uint32_t n, const uint8_t *arena, uint32_t *counts,
-                                HdrStop *stops, unsigned long long *bytes)
+template <bool CBC>
+__global__ void in_count_kernel(const tlsrec_stream_in *s, uint32_t n, const uint8_t *arena, const SlotState *slots,
+                                uint32_t cap, uint32_t *counts, HdrStop *stops, unsigned long long *bytes)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long b = 0;
     if (i < n) {
         uint32_t c = 0;
-        const HdrStop st = walk_in(arena + s[i].off, s[i].len,
+        const HdrStop st = walk_in(arena + s[i].off, s[i].len, rx_limit<CBC>(slots, cap, s[i].slot),
                                    [&](uint32_t, uint32_t, uint32_t, uint8_t, uint8_t, uint32_t dlen) { c++; b += dlen; });
         counts[i] = c;
         stops[i] = st;
@@ -174,6 +202,7 @@ __device__ __forceinline__ tlsrec_batch_rec rx_desc(const tlsrec_stream_in &si, 
     return d;
 }
 
+template <bool CBC>
 __global__ void in_emit_kernel(const tlsrec_stream_in *s, uint32_t n, const uint8_t *arena, const uint32_t *offs,
                                const SlotState *slots, uint32_t cap, tlsrec_batch_rec *recs, uint32_t max_records,
                                tlsrec_batch_res *res)
@@ -181,10 +210,12 @@ __global__ void in_emit_kernel(const tlsrec_stream_in *s, uint32_t n, const uint
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const tlsrec_stream_in si = s[i];
-    const bool tls13 = slot_minor(slots, cap, si.slot) == 4;
+    const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
     uint64_t seq = be64(si.in_ctr);
     tlsrec_batch_rec *out = recs + offs[i];
-    walk_in(arena + si.off, si.len, [&](uint32_t k, uint32_t pos, uint32_t type, uint8_t v0, uint8_t v1, uint32_t dlen) {
+    const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
+    walk_in(arena + si.off, si.len, lim,
+            [&](uint32_t k, uint32_t pos, uint32_t type, uint8_t v0, uint8_t v1, uint32_t dlen) {
         const tlsrec_batch_rec d = rx_desc(si, tls13, pos, type, v0, v1, dlen, seq);
         if (!(tls13 && type == 20)) seq++;                  /* (a TLS 1.3 CCS takes no number) */
         if (offs[i] + k < max_records) {                /* (launched before the host has checked the total) */
@@ -194,6 +225,7 @@ __global__ void in_emit_kernel(const tlsrec_stream_in *s, uint32_t n, const uint
     });
 }
 
+template <bool CBC>
 __global__ void in_finish_kernel(const tlsrec_stream_in *s, uint32_t n, const uint32_t *offs, const uint32_t *counts,
                                  const HdrStop *stops, const SlotState *slots, uint32_t cap,
                                  const tlsrec_batch_rec *recs, tlsrec_batch_res *res, tlsrec_stream_in_res *sres)
@@ -201,7 +233,7 @@ __global__ void in_finish_kernel(const tlsrec_stream_in *s, uint32_t n, const ui
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const tlsrec_stream_in si = s[i];
-    const uint32_t minor = slot_minor(slots, cap, si.slot);
+    const uint32_t minor = slot_minor<CBC>(slots, cap, si.slot);
     uint64_t ctr = be64(si.in_ctr);
     uint32_t nbz = si.nb_zero, nrec = 0, consumed = 0;
     int32_t st = 0;
@@ -303,8 +335,9 @@ struct RxHdr {
     uint8_t v0, v1;
 };
 
-/* the header at q checked as walk_in does, and of length want */
-__device__ __forceinline__ RxHdr rx_header(const uint8_t *base, uint32_t len, uint64_t q, uint32_t want, int32_t *err)
+/* the header at q checked as walk_in does (lim: its limit), and of length want */
+__device__ __forceinline__ RxHdr rx_header(const uint8_t *base, uint32_t len, uint64_t q, uint32_t want, uint32_t lim,
+                                           int32_t *err)
 {
     RxHdr h = { false, (uint32_t) q, 0, 0, 0, 0 };
     *err = 0;
@@ -317,7 +350,7 @@ __device__ __forceinline__ RxHdr rx_header(const uint8_t *base, uint32_t len, ui
     const uint32_t ver = ((uint32_t) h.v0 << 8) | h.v1;
     if (h.type < 20 || h.type > 23 || ver > (uint32_t) MAX_VERSION || h.dlen == 0)
         *err = TLSREC_ERR_SSL_INVALID_RECORD;                          /* :3529-3539, :3723-3726 */
-    else if (5 + h.dlen > TLSREC_MAX_IN_RECORD)
+    else if (5 + h.dlen > lim)
         *err = TLSREC_ERR_SSL_BAD_INPUT_DATA;
     else
         h.ok = (uint64_t) len - q >= 5 + h.dlen && h.dlen == want;
@@ -328,7 +361,8 @@ __device__ __forceinline__ RxHdr rx_header(const uint8_t *base, uint32_t len, ui
  * ccs_before = the TLS 1.3 CCS records before it (tls13 only: they take no
  * sequence number).  Returns the stop and the record count (group-uniform). */
 template <int G = RG, typename F>
-__device__ HdrStop group_walk(const uint8_t *base, uint32_t len, int lane, bool tls13, uint32_t *count, F f)
+__device__ HdrStop group_walk(const uint8_t *base, uint32_t len, int lane, bool tls13, uint32_t lim, uint32_t *count,
+                              F f)
 {
     const int q = lane & (G - 1);
     uint32_t p = 0, k = 0, nccs = 0;
@@ -337,7 +371,7 @@ __device__ HdrStop group_walk(const uint8_t *base, uint32_t len, int lane, bool 
         const uint32_t dlen0 = ((uint32_t) base[p + 3] << 8) | base[p + 4];
         const uint64_t at = (uint64_t) p + (uint64_t) q * (5 + dlen0);
         int32_t err;
-        const RxHdr h = rx_header(base, len, at, dlen0, &err);
+        const RxHdr h = rx_header(base, len, at, dlen0, lim, &err);
         const uint32_t okm = group_ballot<G>(h.ok, lane);
         const uint32_t m = (uint32_t) __builtin_ctz(~okm);                 /* leading records */
         if (m == 0) {                                                      /* the header at p itself */
@@ -358,10 +392,11 @@ __device__ HdrStop group_walk(const uint8_t *base, uint32_t len, int lane, bool 
 /* G lanes per connection: 16, or 4 / 8 when the caller's max_records says
  * connections hold that few records (r06: a 4-record stream left 12 of 16
  * lanes idle, four times the waves the walk needed) */
-template <int G>
+template <int G, bool CBC>
 __global__ __launch_bounds__(RX_THREADS) void in_count_group_kernel(const tlsrec_stream_in *s, uint32_t n,
-                                                                    const uint8_t *arena, uint32_t *counts,
-                                                                    HdrStop *stops, unsigned long long *bytes)
+                                                                    const uint8_t *arena, const SlotState *slots,
+                                                                    uint32_t cap, uint32_t *counts, HdrStop *stops,
+                                                                    unsigned long long *bytes)
 {
     const int tid = threadIdx.x, lane = tid & 63, q = tid & (G - 1);
     const uint32_t i = blockIdx.x * (RX_THREADS / G) + (uint32_t) (tid / G);
@@ -369,8 +404,8 @@ __global__ __launch_bounds__(RX_THREADS) void in_count_group_kernel(const tlsrec
     if (i < n) {
         const tlsrec_stream_in si = s[i];
         uint32_t cnt = 0;
-        const HdrStop st = group_walk<G>(arena + si.off, si.len, lane, false, &cnt,
-                                      [&](uint32_t, const RxHdr &h, uint32_t) { b += h.dlen; });
+        const HdrStop st = group_walk<G>(arena + si.off, si.len, lane, false, rx_limit<CBC>(slots, cap, si.slot), &cnt,
+                                         [&](uint32_t, const RxHdr &h, uint32_t) { b += h.dlen; });
         if (q == 0) {
             counts[i] = cnt;
             stops[i] = st;
@@ -381,7 +416,7 @@ __global__ __launch_bounds__(RX_THREADS) void in_count_group_kernel(const tlsrec
     wave_add_bytes(bytes, b);
 }
 
-template <int G>
+template <int G, bool CBC>
 __global__ __launch_bounds__(RX_THREADS) void in_emit_group_kernel(const tlsrec_stream_in *s, uint32_t n,
                                                                    const uint8_t *arena, const uint32_t *offs,
                                                                    const SlotState *slots, uint32_t cap,
@@ -392,11 +427,12 @@ __global__ __launch_bounds__(RX_THREADS) void in_emit_group_kernel(const tlsrec_
     const uint32_t i = blockIdx.x * (RX_THREADS / G) + (uint32_t) (tid / G);
     if (i >= n) return;
     const tlsrec_stream_in si = s[i];
-    const bool tls13 = slot_minor(slots, cap, si.slot) == 4;
+    const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
     const uint64_t seq0 = be64(si.in_ctr);
     tlsrec_batch_rec *out = recs + offs[i];
+    const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
     uint32_t cnt;
-    group_walk<G>(arena + si.off, si.len, lane, tls13, &cnt, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
+    group_walk<G>(arena + si.off, si.len, lane, tls13, lim, &cnt, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
         /* in_ctr + the records before that took a number */
         const tlsrec_batch_rec d = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
         if (offs[i] + k < max_records) {                /* (launched before the host has checked the total) */
@@ -506,7 +542,7 @@ __device__ __forceinline__ uint32_t claim_tile(uint32_t *ctr, uint32_t *sh)
 #ifndef TLSREC_RX_FRAME_NT
 #define TLSREC_RX_FRAME_NT 512
 #endif
-template <int G, int CH, int NT>
+template <int G, int CH, int NT, bool CBC>
 __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s, uint32_t n,
                                                               const uint8_t *arena, const SlotState *slots,
                                                               uint32_t cap, uint32_t *counts, uint32_t *offs,
@@ -527,8 +563,8 @@ __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s,
         uint32_t cnt = 0;
         if (i < n) {
             const tlsrec_stream_in si = s[i];
-            const HdrStop st = group_walk<G>(arena + si.off, si.len, lane, false, &cnt,
-                                          [&](uint32_t, const RxHdr &h, uint32_t) { b += h.dlen; });
+            const HdrStop st = group_walk<G>(arena + si.off, si.len, lane, false, rx_limit<CBC>(slots, cap, si.slot),
+                                             &cnt, [&](uint32_t, const RxHdr &h, uint32_t) { b += h.dlen; });
             if (q == 0) {
                 counts[i] = cnt;
                 stops[i] = st;
@@ -571,11 +607,13 @@ __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s,
         const uint32_t cnt = sh_cnt[c * RX_CONNS_G + g], off = sh_off[c * RX_CONNS_G + g];
         if (i >= n || !cnt) continue;                     /* group-uniform */
         const tlsrec_stream_in si = s[i];
-        const bool tls13 = slot_minor(slots, cap, si.slot) == 4;
+        const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
         const uint64_t seq0 = be64(si.in_ctr);
         tlsrec_batch_rec *out = recs + off;
+        const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
         uint32_t c2;
-        group_walk<G>(arena + si.off, si.len, lane, tls13, &c2, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
+        group_walk<G>(arena + si.off, si.len, lane, tls13, lim, &c2,
+                      [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
             if (off + k >= max_records) return;
             out[k] = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
             guard_result(&res[off + k]);
@@ -588,14 +626,25 @@ struct OutShape {
     uint32_t ok;              /* slot usable */
     uint32_t head;            /* explicit-IV room before the content (8 for TLS 1.2 GCM / CCM) */
     uint32_t tls13, gran, tag;
+    uint32_t cbc;             /* 0 = an AEAD slot; 1 = AES-CBC MAC-then-encrypt, 2 = encrypt-then-MAC: head is
+                                 the 16-byte explicit IV and tag the MAC length */
 };
 
+template <bool CBC>
 __device__ __forceinline__ OutShape out_shape(const SlotState *slots, uint32_t cap, uint32_t slot)
 {
-    OutShape o = { 0, 0, 0, 16, 16 };
+    OutShape o = { 0, 0, 0, 16, 16, 0 };
     if (slot >= cap) return o;
     const tlsrec_key_material &k = slots[slot].km;
-    if (!k.cipher || k.cipher > TLSREC_CIPHER_MAX) return o;   /* (a CBC slot: as never loaded) */
+    if (CBC && cbc_is_cipher(k.cipher)) {          /* (km.reserved[1] the MAC, [2] the MAC order: cbc.hip) */
+        o.ok = 1;
+        o.head = 16;
+        o.gran = TLSREC_PADDING_GRANULARITY;
+        o.tag = cbc_maclen(k.reserved[1]);
+        o.cbc = 1u + k.reserved[2];
+        return o;
+    }
+    if (!k.cipher || k.cipher > TLSREC_CIPHER_MAX) return o;   /* (!CBC, a CBC slot: as never loaded) */
     o.ok = 1;
     o.tls13 = k.tls_minor == 4;
     o.head = (!o.tls13 && k.fixed_ivlen == 4) ? 8u : 0u;
@@ -645,7 +694,10 @@ struct TlsWire {
     static __device__ __forceinline__ bool past_wrap(uint64_t ctr0, uint64_t k) { return k > ~ctr0; }
     static __device__ __forceinline__ uint64_t ctr_of(uint64_t ctr0, uint64_t k) { return ctr0 + k; }
     static __device__ __forceinline__ bool step(uint64_t &ctr) { return ++ctr == 0; }        /* :2749-2756 */
-    static __device__ __forceinline__ uint32_t buf_len(uint32_t) { return TLSREC_OUT_BUF_SPACE; }
+    static __device__ __forceinline__ uint32_t buf_len(uint32_t, bool cbc)
+    {
+        return cbc ? TLSREC_OUT_BUF_SPACE_CBC : TLSREC_OUT_BUF_SPACE;     /* by the slot's kind */
+    }
     static __device__ __forceinline__ void header(uint8_t *h, const tlsrec_stream_out &si, const OutShape &sh,
                                                   const SlotState *, uint32_t, const uint8_t *, uint32_t body)
     {
@@ -684,9 +736,10 @@ struct DtlsWire {
         ctr = ctr_of(ctr, 1);
         return (ctr & M48) == 0;
     }
-    static __device__ __forceinline__ uint32_t buf_len(uint32_t hdr)
+    static __device__ __forceinline__ uint32_t buf_len(uint32_t hdr, bool cbc)
     {
-        return TLSREC_DTLS_OUT_BUFFER_LEN - hdr;         /* out_buf_len - (out_iv - out_buf) */
+        /* out_buf_len - (out_iv - out_buf), by the slot's kind */
+        return (cbc ? TLSREC_DTLS_OUT_BUFFER_LEN_CBC : TLSREC_DTLS_OUT_BUFFER_LEN) - hdr;
     }
     /* type after encryption, FE FD, epoch + sequence, out_cid, protected length (:2669-2727) */
     static __device__ __forceinline__ void header(uint8_t *h, const tlsrec_stream_out &si, const OutShape &,
@@ -704,20 +757,22 @@ struct DtlsWire {
 };
 
 /* what the send kernels need of a connection, computed once per thread */
-template <typename W>
+template <typename W, bool CBC = false>
 struct SendConn {
     uint32_t frag;            /* (first: its load is issued before out_shape's dependent ones) */
     OutShape sh;
     uint32_t cid, hdr;
 
     __device__ __forceinline__ SendConn(const tlsrec_stream_out &si, const SlotState *slots, uint32_t cap)
-        : frag(frag_of(si)), sh(out_shape(slots, cap, si.slot)), cid(W::cid_len(sh, slots, si.slot)),
+        : frag(frag_of(si)), sh(out_shape<CBC>(slots, cap, si.slot)), cid(W::cid_len(sh, slots, si.slot)),
           hdr(W::hdr(cid))
     {
     }
     /* protected length of an n-byte record */
     __device__ __forceinline__ uint32_t body(uint32_t n) const
     {
+        /* a CBC slot: the reference's length for that MAC, MAC order and (with a CID) inner plaintext */
+        if (CBC && sh.cbc) return cbc_body_len(sh.tag, sh.cbc == 2, W::padded(sh, cid) ? inner_len(n, sh.gran) : n);
         return W::body(sh.head, sh.tag, sh.gran, W::padded(sh, cid), n);
     }
     /* content bytes of record k */
@@ -728,7 +783,7 @@ struct SendConn {
     }
 };
 
-template <typename W>
+template <typename W, bool CBC>
 __global__ void send_count_kernel(const tlsrec_stream_out *s, uint32_t n, const SlotState *slots, uint32_t cap,
                                   uint32_t *counts, unsigned long long *bytes)
 {
@@ -736,7 +791,7 @@ __global__ void send_count_kernel(const tlsrec_stream_out *s, uint32_t n, const 
     unsigned long long b = 0;
     if (i < n) {
         const uint32_t f = frag_of(s[i]);
-        const bool ok = W::usable(out_shape(slots, cap, s[i].slot));
+        const bool ok = W::usable(out_shape<CBC>(slots, cap, s[i].slot));
         counts[i] = ok ? (uint32_t) (((uint64_t) s[i].in_len + f - 1) / f) : 0u;
         b = ok ? s[i].in_len : 0;
     } else if (i == n) {
@@ -768,11 +823,14 @@ __global__ void __launch_bounds__(256) out_map_kernel(uint32_t n, const uint32_t
  * this kernel took 0.36-0.43 ms of a 2 ms send of 1 M records). */
 /* record k (= j - offs[i]) of connection i: header, descriptor, and the
  * content (srcoff: its offset for the AEAD to read in place; else copied
- * into the record's slot by the LPR lanes) */
-template <typename W, int LPR>
-__device__ __forceinline__ void send_frame_one(const tlsrec_stream_out &si, const SendConn<W> &c, uint32_t k,
+ * into the record's slot by the LPR lanes); in the CBC kernels a CBC slot's
+ * record also takes its explicit IV from ivs[16 j .. 16 j + 16), placed at
+ * buf_off + data_offset - 16 where the CBC batch kernel reads the caller's IV */
+template <typename W, int LPR, bool CBC>
+__device__ __forceinline__ void send_frame_one(const tlsrec_stream_out &si, const SendConn<W, CBC> &c, uint32_t k,
                                                uint32_t j, uint32_t lane, const SlotState *slots, const uint8_t *in,
-                                               uint8_t *out, tlsrec_batch_rec *recs, uint64_t *srcoff)
+                                               uint8_t *out, tlsrec_batch_rec *recs, uint64_t *srcoff,
+                                               const uint8_t *ivs)
 {
     const uint64_t src_off = (uint64_t) k * c.frag;
     const uint32_t len = c.len(si, k);
@@ -804,12 +862,17 @@ __device__ __forceinline__ void send_frame_one(const tlsrec_stream_out &si, cons
         for (uint32_t b = nv * 16 + lane; b < len; b += LPR) dst[b] = src[b];
     }
     if (lane == 0) {
+        if (CBC && c.sh.cbc) {
+            uint4 iv;
+            __builtin_memcpy(&iv, ivs + 16 * (uint64_t) j, 16);
+            __builtin_memcpy(out + pos + c.hdr, &iv, 16);
+        }
         tlsrec_batch_rec d;
         memset(&d, 0, sizeof(d));
         put_be64(d.ctr, W::ctr_of(be64(si.out_ctr), k));
         W::header(out + pos, si, c.sh, slots, c.cid, d.ctr, c.body(len));
         d.buf_off = pos + c.hdr;                   /* rec.buf = out_iv */
-        d.buf_len = W::buf_len(c.hdr);
+        d.buf_len = W::buf_len(c.hdr, CBC && c.sh.cbc);
         d.data_offset = c.sh.head;                 /* out_msg - out_iv */
         d.data_len = len;
         d.slot = si.slot;
@@ -821,17 +884,17 @@ __device__ __forceinline__ void send_frame_one(const tlsrec_stream_out &si, cons
 }
 
 /* the copy path, after out_map_kernel */
-template <typename W, int LPR>
+template <typename W, int LPR, bool CBC>
 __global__ void __launch_bounds__(256) send_frame_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs,
                                                          uint32_t total, const SlotState *slots, uint32_t cap,
                                                          const uint8_t *in, uint8_t *out, tlsrec_batch_rec *recs,
-                                                         uint64_t *srcoff)
+                                                         uint64_t *srcoff, const uint8_t *ivs)
 {
     const uint32_t j = blockIdx.x * (256 / LPR) + threadIdx.x / LPR, lane = threadIdx.x % LPR;
     if (j >= total) return;
     const uint32_t i = recs[j].slot;              /* connection of record j (out_map_kernel) */
     const uint32_t k = j - offs[i];
-    send_frame_one<W, LPR>(s[i], SendConn<W>(s[i], slots, cap), k, j, lane, slots, in, out, recs, srcoff);
+    send_frame_one<W, LPR, CBC>(s[i], SendConn<W, CBC>(s[i], slots, cap), k, j, lane, slots, in, out, recs, srcoff, ivs);
 }
 
 /* (r06) The in-place send frame (srcoff) with a group of RG lanes per
@@ -851,10 +914,11 @@ __global__ void __launch_bounds__(RX_THREADS) out_frame_conn_kernel(const tlsrec
     const tlsrec_stream_out si = s[i];
     const uint32_t first = offs[i], cnt = counts[i];
     const SendConn<W> c(si, slots, cap);
-    for (uint32_t k = q; k < cnt; k += RG) send_frame_one<W, 1>(si, c, k, first + k, 0, slots, in, out, recs, srcoff);
+    for (uint32_t k = q; k < cnt; k += RG)
+        send_frame_one<W, 1, false>(si, c, k, first + k, 0, slots, in, out, recs, srcoff, nullptr);
 }
 
-template <typename W>
+template <typename W, bool CBC>
 __global__ void send_finish_kernel(const tlsrec_stream_out *s, uint32_t n, const uint32_t *offs,
                                    const uint32_t *counts, const SlotState *slots, uint32_t cap,
                                    const tlsrec_batch_res *res, tlsrec_stream_out_res *sres)
@@ -862,7 +926,7 @@ __global__ void send_finish_kernel(const tlsrec_stream_out *s, uint32_t n, const
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const tlsrec_stream_out si = s[i];
-    const SendConn<W> c(si, slots, cap);
+    const SendConn<W, CBC> c(si, slots, cap);
     uint64_t ctr = be64(si.out_ctr);
     int32_t st = W::usable(c.sh) || si.in_len == 0 ? 0 : TLSREC_ERR_SSL_BAD_INPUT_DATA;
     uint32_t nrec = 0, olen = 0;
@@ -960,9 +1024,15 @@ __device__ __forceinline__ uint32_t read_version_dtls(uint32_t a, uint32_t b)
     return (uint16_t) ~(w - (w == 0xfeffu ? 0x0202u : 0x0201u));
 }
 
-__device__ __forceinline__ uint32_t dgram_len(const tlsrec_dgram &d)
+/* maxdg: TLSREC_DTLS_MAX_DATAGRAM(_CBC) by the connection's slot kind (dg_limit) */
+__device__ __forceinline__ uint32_t dgram_len(const tlsrec_dgram &d, uint32_t maxdg)
 {
-    return d.len < TLSREC_DTLS_MAX_DATAGRAM ? d.len : (uint32_t) TLSREC_DTLS_MAX_DATAGRAM;   /* f_recv truncates */
+    return d.len < maxdg ? d.len : maxdg;   /* f_recv truncates */
+}
+template <bool CBC>
+__device__ __forceinline__ uint32_t dg_limit(const SlotState *slots, uint32_t cap, uint32_t slot)
+{
+    return slot_limit<CBC>(slots, cap, slot, TLSREC_DTLS_MAX_DATAGRAM, TLSREC_DTLS_MAX_DATAGRAM_CBC);
 }
 
 /* The records of one datagram, walked with the header checks of
@@ -1030,7 +1100,7 @@ __device__ __forceinline__ int32_t dtls_walk_pre(const uint8_t *b, uint32_t len,
  * per record, fd(stop) per datagram. */
 template <int U, typename FR, typename FD, typename FC>
 __device__ __forceinline__ void dtls_conn_walk(uint32_t d0, uint32_t d1, const tlsrec_dgram *dg, const uint8_t *arena,
-                                               uint32_t cid_conf, FR fr, FD fd, FC fc)
+                                               uint32_t cid_conf, uint32_t maxdg, FR fr, FD fd, FC fc)
 {
     for (uint32_t d = d0; d < d1; d += U) {
         fc();                                   /* the caller's own loads for the next U datagrams */
@@ -1044,7 +1114,7 @@ __device__ __forceinline__ void dtls_conn_walk(uint32_t d0, uint32_t d1, const t
             if (d + u < d1) {
                 const tlsrec_dgram g = dg[d + u];
                 off[u] = g.off;
-                len[u] = dgram_len(g);
+                len[u] = dgram_len(g, maxdg);
             }
         }
 #pragma unroll
@@ -1100,13 +1170,15 @@ struct ReplayWindow {
     }
 };
 
+template <bool CBC>
 __device__ __forceinline__ bool dtls_conn_ok(const tlsrec_dtls_in &c, uint32_t ndg, const SlotState *slots,
                                              uint32_t cap)
 {
-    return slot_minor(slots, cap, c.slot) == 3 && c.first_dgram <= ndg && c.ndgram <= ndg - c.first_dgram &&
+    return slot_minor<CBC>(slots, cap, c.slot) == 3 && c.first_dgram <= ndg && c.ndgram <= ndg - c.first_dgram &&
            c.cid_len <= TLSREC_CID_LEN_MAX;
 }
 
+template <bool CBC>
 __global__ void dtls_count_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsrec_dgram *dg, uint32_t ndg,
                                   const uint8_t *arena, const SlotState *slots, uint32_t cap, uint32_t *counts,
                                   unsigned long long *bytes)
@@ -1116,9 +1188,10 @@ __global__ void dtls_count_kernel(const tlsrec_dtls_in *c, uint32_t n, const tls
     if (i < n) {
         const tlsrec_dtls_in ci = c[i];
         uint32_t cnt = 0;
-        if (dtls_conn_ok(ci, ndg, slots, cap))
+        const uint32_t maxdg = dg_limit<CBC>(slots, cap, ci.slot);
+        if (dtls_conn_ok<CBC>(ci, ndg, slots, cap))
             for (uint32_t d = ci.first_dgram; d < ci.first_dgram + ci.ndgram; d++)
-                dtls_walk(arena + dg[d].off, dgram_len(dg[d]), ci.cid_len, [&](const DtlsHdr &h, const uint8_t *) {
+                dtls_walk(arena + dg[d].off, dgram_len(dg[d], maxdg), ci.cid_len, [&](const DtlsHdr &h, const uint8_t *) {
                     cnt++;
                     b += h.data_len;
                 });
@@ -1133,6 +1206,7 @@ __global__ void dtls_count_kernel(const tlsrec_dtls_in *c, uint32_t n, const tls
  * and the window the connection arrived with does not reject it: the window
  * only ever gains records, so every record the in-order pass will accept is
  * among them (replayed copies of a record that then fails its MAC included). */
+template <bool CBC>
 __global__ void dtls_emit_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsrec_dgram *dg, uint32_t ndg,
                                  const uint8_t *arena, const uint32_t *offs, const SlotState *slots, uint32_t cap,
                                  tlsrec_batch_rec *recs, uint32_t max_records, tlsrec_batch_res *res)
@@ -1140,12 +1214,13 @@ __global__ void dtls_emit_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsr
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const tlsrec_dtls_in ci = c[i];
-    if (!dtls_conn_ok(ci, ndg, slots, cap)) return;
+    if (!dtls_conn_ok<CBC>(ci, ndg, slots, cap)) return;
     const ReplayWindow w0 = { ci.window_top, ci.window, (ci.flags & TLSREC_DTLS_ANTI_REPLAY) != 0 };
+    const uint32_t maxdg = dg_limit<CBC>(slots, cap, ci.slot);
     uint32_t k = offs[i];
     for (uint32_t d = ci.first_dgram; d < ci.first_dgram + ci.ndgram; d++) {
         const uint64_t base = dg[d].off;
-        dtls_walk(arena + base, dgram_len(dg[d]), ci.cid_len, [&](const DtlsHdr &h, const uint8_t *p) {
+        dtls_walk(arena + base, dgram_len(dg[d], maxdg), ci.cid_len, [&](const DtlsHdr &h, const uint8_t *p) {
             tlsrec_batch_rec r;
             memset(&r, 0, sizeof(r));
             r.buf_off = base + h.pos;                  /* rec->buf = the header (:3715-3716) */
@@ -1177,7 +1252,7 @@ __global__ void dtls_emit_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsr
  * without a second walk over the header lines (r06; a connection with more
  * records walks again). */
 constexpr int DG_THREADS = 256;
-template <int S>
+template <int S, bool CBC>
 __global__ __launch_bounds__(DG_THREADS) void dtls_frame_kernel(const tlsrec_dtls_in *c, uint32_t n,
                                                                 const tlsrec_dgram *dg, uint32_t ndg,
                                                                 const uint8_t *arena, const SlotState *slots,
@@ -1199,10 +1274,11 @@ __global__ __launch_bounds__(DG_THREADS) void dtls_frame_kernel(const tlsrec_dtl
     bool ok = false;
     if (i < n) {
         ci = c[i];
-        ok = dtls_conn_ok(ci, ndg, slots, cap);
+        ok = dtls_conn_ok<CBC>(ci, ndg, slots, cap);
         if (ok) {
             uint32_t d = ci.first_dgram, kd = 0;
             dtls_conn_walk<DG_U>(ci.first_dgram, ci.first_dgram + ci.ndgram, dg, arena, ci.cid_len,
+                                 dg_limit<CBC>(slots, cap, ci.slot),
                                  [&](uint64_t base, const DtlsHdr &h, const uint8_t *p) {
                                      if (S > 0 && cnt < (uint32_t) S) {
                                          const uint64_t bo = base + h.pos;
@@ -1296,6 +1372,7 @@ __global__ __launch_bounds__(DG_THREADS) void dtls_frame_kernel(const tlsrec_dtl
     }
     uint32_t k = off, d = ci.first_dgram, kd = off;
     dtls_conn_walk<DG_U>(ci.first_dgram, ci.first_dgram + ci.ndgram, dg, arena, ci.cid_len,
+                         dg_limit<CBC>(slots, cap, ci.slot),
                          [&](uint64_t base, const DtlsHdr &h, const uint8_t *p) {
                              if (recs && k < max_records) {
                                  tlsrec_batch_rec r;
@@ -1347,7 +1424,7 @@ __device__ __forceinline__ void dtls_unreach_wipe(uint8_t *arena, const tlsrec_b
  * the decrypt results (one lane).  PRE: the datagrams DG_U at a time
  * (dtls_conn_walk), the records' results and descriptor slots loaded with
  * them. */
-template <bool PRE>
+template <bool PRE, bool CBC>
 __device__ void dtls_finish_one(uint32_t i, const tlsrec_dtls_in *c, const tlsrec_dgram *dg, uint32_t ndg,
                                 uint8_t *arena, const uint32_t *offs, const uint32_t *counts,
                                 const SlotState *slots, uint32_t cap, const tlsrec_batch_rec *recs,
@@ -1465,7 +1542,7 @@ __device__ void dtls_finish_one(uint32_t i, const tlsrec_dtls_in *c, const tlsre
         if (!st) done++;
         dropped = false;
     };
-    if (!dtls_conn_ok(ci, ndg, slots, cap)) {
+    if (!dtls_conn_ok<CBC>(ci, ndg, slots, cap)) {
         st = TLSREC_ERR_SSL_BAD_INPUT_DATA;
     } else if (PRE && dgst) {
         /* the frame kernel's datagram summaries; each record's epoch and
@@ -1503,10 +1580,11 @@ __device__ void dtls_finish_one(uint32_t i, const tlsrec_dtls_in *c, const tlsre
         }
     } else if constexpr (PRE) {
         dtls_conn_walk<DGF_U>(ci.first_dgram, ci.first_dgram + ci.ndgram, dg, arena, ci.cid_len,
-                             [&](uint64_t, const DtlsHdr &, const uint8_t *p) { hdr_rec(p); }, ondgram, prefetch);
+                              dg_limit<CBC>(slots, cap, ci.slot),
+                              [&](uint64_t, const DtlsHdr &, const uint8_t *p) { hdr_rec(p); }, ondgram, prefetch);
     } else {
         for (uint32_t d = ci.first_dgram; d < ci.first_dgram + ci.ndgram; d++)
-            ondgram(dtls_walk(arena + dg[d].off, dgram_len(dg[d]), ci.cid_len,
+            ondgram(dtls_walk(arena + dg[d].off, dgram_len(dg[d], dg_limit<CBC>(slots, cap, ci.slot)), ci.cid_len,
                               [&](const DtlsHdr &, const uint8_t *p) { hdr_rec(p); }));
     }
     tlsrec_dtls_in_res o;
@@ -1524,7 +1602,7 @@ __device__ void dtls_finish_one(uint32_t i, const tlsrec_dtls_in *c, const tlsre
     cres[i] = o;
 }
 
-template <bool PRE>
+template <bool PRE, bool CBC>
 __global__ void dtls_finish_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsrec_dgram *dg, uint32_t ndg,
                                    uint8_t *arena, const uint32_t *offs, const uint32_t *counts,
                                    const SlotState *slots, uint32_t cap, const tlsrec_batch_rec *recs,
@@ -1532,7 +1610,7 @@ __global__ void dtls_finish_kernel(const tlsrec_dtls_in *c, uint32_t n, const tl
                                    const uint32_t *dgst)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dtls_finish_one<PRE>(i, c, dg, ndg, arena, offs, counts, slots, cap, recs, res, disp, cres, dgst);
+    if (i < n) dtls_finish_one<PRE, CBC>(i, c, dg, ndg, arena, offs, counts, slots, cap, recs, res, disp, cres, dgst);
 }
 
 /* The batch's record count and byte total to the host (r06): one wave sums
@@ -1759,12 +1837,36 @@ static int scan_total(Scratch &sc, uint32_t n, hipStream_t st, uint32_t *total, 
 
 static inline uint32_t blocks(uint32_t n, uint32_t t) { return (n + t - 1) / t; }
 
-extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_stream_in *streams, uint32_t nstreams,
-                                     uint8_t *arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
-                                     uint32_t max_records, tlsrec_stream_in_res *sres, uint32_t *nrecords,
-                                     void *stream)
+/* The _ex calls' options: *cbc = TLSREC_FRAME_CBC asked for (opts == NULL:
+ * the plain call).  Unknown flag bits, reserved != 0, or a send call with the
+ * flag and no IV array: BAD_INPUT_DATA, before anything is launched. */
+static int frame_opts(const tlsrec_frame_opts *opts, bool send, bool *cbc)
+{
+    *cbc = false;
+    if (!opts) return 0;
+    if ((opts->flags & ~TLSREC_FRAME_CBC) || opts->reserved) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    *cbc = (opts->flags & TLSREC_FRAME_CBC) != 0;
+    if (send && *cbc && !opts->cbc_ivs) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    return 0;
+}
+
+/* f(std::bool_constant<cbc>) for the kernels' CBC template argument */
+template <typename F>
+static void with_cbc(bool cbc, F f)
+{
+    if (cbc) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+extern "C" int tlsrec_stream_decrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_in *streams, uint32_t nstreams,
+                                        uint8_t *arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
+                                        uint32_t max_records, tlsrec_stream_in_res *sres, uint32_t *nrecords,
+                                        void *stream, const tlsrec_frame_opts *opts)
 {
     if (nrecords) *nrecords = 0;
+    bool cbc;
+    if (const int orc = frame_opts(opts, false, &cbc)) return orc;
+    cbc = cbc && tlsrec__keytab_has_cbc(kt);      /* (a table without CBC slots: the plain call's kernels) */
     if (!kt || (nstreams && (!streams || !arena || !sres))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (nstreams == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
@@ -1787,22 +1889,29 @@ extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_strea
         /* tiles of 128 connections: one chunk of 128 at 4 lanes (512 threads),
          * or chunks of 64 / 32 at 8 / 16 lanes */
         with_rx_group(rg, [&](auto G) {
-            constexpr int FNT = TLSREC_RX_FRAME_NT;
-            hipLaunchKernelGGL((in_frame_kernel<G(), (G() * 128) / FNT, FNT>), dim3(tiles), dim3(FNT), 0, st, streams,
-                               nstreams, ar, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes, sc.tstat, sc.tctr,
-                               recs, (recs && res) ? max_records : 0u, res);
+            with_cbc(cbc, [&](auto C) {
+                constexpr int FNT = TLSREC_RX_FRAME_NT;
+                hipLaunchKernelGGL((in_frame_kernel<G(), (G() * 128) / FNT, FNT, C()>), dim3(tiles), dim3(FNT), 0, st,
+                                   streams, nstreams, ar, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes, sc.tstat,
+                                   sc.tctr, recs, (recs && res) ? max_records : 0u, res);
+            });
         });
         r = hipGetLastError() == hipSuccess ? fetch_total(sc, nstreams, st, &total, &avg)
                                             : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     } else if (r == 0) {
         if (gw)
             with_rx_group(rg, [&](auto G) {
-                hipLaunchKernelGGL(in_count_group_kernel<G()>, dim3(blocks(nstreams + 1, RX_THREADS / G())),
-                                   dim3(RX_THREADS), 0, st, streams, nstreams, ar, sc.counts, sc.stops, sc.bytes);
+                with_cbc(cbc, [&](auto C) {
+                    hipLaunchKernelGGL((in_count_group_kernel<G(), C()>), dim3(blocks(nstreams + 1, RX_THREADS / G())),
+                                       dim3(RX_THREADS), 0, st, streams, nstreams, ar, slots, cap, sc.counts, sc.stops,
+                                       sc.bytes);
+                });
             });
         else
-            hipLaunchKernelGGL(in_count_kernel, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams, nstreams,
-                               ar, sc.counts, sc.stops, sc.bytes);
+            with_cbc(cbc, [&](auto C) {
+                hipLaunchKernelGGL(in_count_kernel<C()>, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams,
+                                   nstreams, ar, slots, cap, sc.counts, sc.stops, sc.bytes);
+            });
         uint64_t seq = 0;
         r = hipGetLastError() == hipSuccess ? scan_publish(sc, nstreams, st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         /* the descriptors are emitted while the host collects the totals
@@ -1810,13 +1919,17 @@ extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_strea
         if (r == 0 && recs && res) {
             if (gw)
                 with_rx_group(rg, [&](auto G) {
-                    hipLaunchKernelGGL(in_emit_group_kernel<G()>, dim3(blocks(nstreams, RX_THREADS / G())),
-                                       dim3(RX_THREADS), 0, st, streams, nstreams, ar, sc.offs, slots, cap, recs,
-                                       max_records, res);
+                    with_cbc(cbc, [&](auto C) {
+                        hipLaunchKernelGGL((in_emit_group_kernel<G(), C()>), dim3(blocks(nstreams, RX_THREADS / G())),
+                                           dim3(RX_THREADS), 0, st, streams, nstreams, ar, sc.offs, slots, cap, recs,
+                                           max_records, res);
+                    });
                 });
             else
-                hipLaunchKernelGGL(in_emit_kernel, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
-                                   ar, sc.offs, slots, cap, recs, max_records, res);
+                with_cbc(cbc, [&](auto C) {
+                    hipLaunchKernelGGL(in_emit_kernel<C()>, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams,
+                                       nstreams, ar, sc.offs, slots, cap, recs, max_records, res);
+                });
             if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         }
         if (r == 0) r = collect_totals(sc, nstreams, st, seq, &total, &avg);
@@ -1825,15 +1938,26 @@ extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_strea
     if (r == 0 && total && (!recs || !res)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (r == 0 && total)
         r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg,
-                                env_flag("TLSREC_RX_PREFILL", true));
+                                env_flag("TLSREC_RX_PREFILL", true), cbc);
     if (r == 0) {
-        hipLaunchKernelGGL(in_finish_kernel, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams, sc.offs,
-                           sc.counts, sc.stops, slots, cap, recs, res, sres);
+        with_cbc(cbc, [&](auto C) {
+            hipLaunchKernelGGL(in_finish_kernel<C()>, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
+                               sc.offs, sc.counts, sc.stops, slots, cap, recs, res, sres);
+        });
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     tlsrec__scratch_release(&sc.lease);
     if (r == 0 && nrecords) *nrecords = total;
     return r;
+}
+
+extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_stream_in *streams, uint32_t nstreams,
+                                     uint8_t *arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
+                                     uint32_t max_records, tlsrec_stream_in_res *sres, uint32_t *nrecords,
+                                     void *stream)
+{
+    return tlsrec_stream_decrypt_ex(kt, streams, nstreams, arena, recs, res, max_records, sres, nrecords, stream,
+                                    nullptr);
 }
 
 /* the output bytes of in_len application bytes: records of max_frag bytes,
@@ -1866,14 +1990,42 @@ extern "C" uint64_t tlsrec_dtls_out_size(int cipher, uint32_t granularity, uint3
                                    max_frag);
 }
 
+/* the same for a CBC slot: cbc_body_len over the content, or with a CID over
+ * the DTLSInnerPlaintext -- SendConn::body's arithmetic */
+static uint64_t send_out_size_cbc(uint64_t hdr, int mac, int etm, bool padded, uint64_t in_len, uint32_t max_frag)
+{
+    const uint64_t ml = cbc_maclen(mac);
+    if (ml == 0 || etm < 0 || etm > 1) return 0;
+    const uint64_t f = max_frag ? max_frag : 16384, g = TLSREC_PADDING_GRANULARITY;
+    const uint64_t full = in_len / f, rest = in_len % f;
+    auto rec = [&](uint64_t n) { return hdr + cbc_body_len(ml, etm != 0, padded ? inner_len(n, g) : n); };
+    return full * rec(f) + (rest ? rec(rest) : 0);
+}
+
+extern "C" uint64_t tlsrec_stream_out_size_cbc(int mac, int etm, uint64_t in_len, uint32_t max_frag)
+{
+    return send_out_size_cbc(5, mac, etm, false, in_len, max_frag);
+}
+
+extern "C" uint64_t tlsrec_dtls_out_size_cbc(int mac, int etm, uint32_t cid_len, uint64_t in_len, uint32_t max_frag)
+{
+    if (cid_len > TLSREC_CID_LEN_MAX) return 0;
+    return send_out_size_cbc(13 + cid_len, mac, etm, cid_len != 0, in_len, max_frag);
+}
+
 /* tlsrec_stream_encrypt / tlsrec_dtls_encrypt: count, scan, frame, the AEAD
  * batch, finish -- the same kernels over the wire format W */
 template <typename W>
 static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
                      const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
-                     uint32_t max_records, tlsrec_stream_out_res *sres, uint32_t *nrecords, void *stream)
+                     uint32_t max_records, tlsrec_stream_out_res *sres, uint32_t *nrecords, void *stream,
+                     const tlsrec_frame_opts *opts)
 {
     if (nrecords) *nrecords = 0;
+    bool cbc;
+    if (const int orc = frame_opts(opts, true, &cbc)) return orc;
+    cbc = cbc && tlsrec__keytab_has_cbc(kt);      /* (a table without CBC slots: the plain call's kernels) */
+    const uint8_t *ivs = cbc ? opts->cbc_ivs : nullptr;
     if (!kt || (nstreams && (!streams || !in_arena || !out_arena || !sres))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (nstreams == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
@@ -1883,8 +2035,10 @@ static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, 
     int r = scratch_alloc(sc, nstreams, st);
     uint32_t total = 0, avg = 0;
     if (r == 0) {
-        hipLaunchKernelGGL(send_count_kernel<W>, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams, nstreams,
-                           slots, cap, sc.counts, sc.bytes);
+        with_cbc(cbc, [&](auto C) {
+            hipLaunchKernelGGL((send_count_kernel<W, C()>), dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams,
+                               nstreams, slots, cap, sc.counts, sc.bytes);
+        });
         r = hipGetLastError() == hipSuccess ? scan_total(sc, nstreams, st, &total, &avg)
                                             : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
@@ -1892,7 +2046,8 @@ static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, 
     if (r == 0 && total && (!recs || !res)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (r == 0 && total) {
         /* AES-GCM / ChaCha20-Poly1305 tables: the AEAD reads the application
-         * data in place (tlsrec__batch_src); other AEADs: copy, then in place */
+         * data in place (tlsrec__batch_src); other AEADs, and any table that
+         * holds a CBC slot: copy, then in place */
         uint64_t *srcoff = nullptr;
         tlsrec_scratch_lease sl = { nullptr, nullptr };
         if (tlsrec__keytab_src_ok(kt) && env_flag("TLSREC_STREAM_SRC", true) &&
@@ -1906,18 +2061,22 @@ static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, 
         } else {
             hipLaunchKernelGGL(out_map_kernel, dim3(blocks(nstreams, 4)), dim3(256), 0, st, nstreams, sc.offs,
                                sc.counts, recs);
-            hipLaunchKernelGGL((send_frame_kernel<W, 64>), dim3(blocks(total, 4)), dim3(256), 0, st, streams, nstreams,
-                               sc.offs, total, slots, cap, in_arena, out_arena, recs, srcoff);
+            with_cbc(cbc, [&](auto C) {
+                hipLaunchKernelGGL((send_frame_kernel<W, 64, C()>), dim3(blocks(total, 4)), dim3(256), 0, st, streams,
+                                   nstreams, sc.offs, total, slots, cap, in_arena, out_arena, recs, srcoff, ivs);
+            });
         }
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         if (r == 0)
             r = srcoff ? tlsrec__batch_src(kt, recs, res, total, in_arena, out_arena, stream, avg, srcoff)
-                       : tlsrec__batch_sized(kt, recs, res, total, out_arena, out_arena, stream, 0, avg, 0);
+                       : tlsrec__batch_sized(kt, recs, res, total, out_arena, out_arena, stream, 0, avg, 0, cbc);
         if (srcoff) tlsrec__scratch_release(&sl);
     }
     if (r == 0) {
-        hipLaunchKernelGGL(send_finish_kernel<W>, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
-                           sc.offs, sc.counts, slots, cap, res, sres);
+        with_cbc(cbc, [&](auto C) {
+            hipLaunchKernelGGL((send_finish_kernel<W, C()>), dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams,
+                               nstreams, sc.offs, sc.counts, slots, cap, res, sres);
+        });
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     tlsrec__scratch_release(&sc.lease);
@@ -1930,7 +2089,17 @@ extern "C" int tlsrec_stream_encrypt(const tlsrec_keytab *kt, const tlsrec_strea
                                      tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
                                      uint32_t *nrecords, void *stream)
 {
-    return send_impl<TlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream);
+    return send_impl<TlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream,
+                              nullptr);
+}
+
+extern "C" int tlsrec_stream_encrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                                        const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
+                                        tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
+                                        uint32_t *nrecords, void *stream, const tlsrec_frame_opts *opts)
+{
+    return send_impl<TlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream,
+                              opts);
 }
 
 extern "C" int tlsrec_dtls_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
@@ -1938,7 +2107,17 @@ extern "C" int tlsrec_dtls_encrypt(const tlsrec_keytab *kt, const tlsrec_stream_
                                    tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
                                    uint32_t *nrecords, void *stream)
 {
-    return send_impl<DtlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream);
+    return send_impl<DtlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream,
+                               nullptr);
+}
+
+extern "C" int tlsrec_dtls_encrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, uint32_t nstreams,
+                                      const uint8_t *in_arena, uint8_t *out_arena, tlsrec_batch_rec *recs,
+                                      tlsrec_batch_res *res, uint32_t max_records, tlsrec_stream_out_res *sres,
+                                      uint32_t *nrecords, void *stream, const tlsrec_frame_opts *opts)
+{
+    return send_impl<DtlsWire>(kt, streams, nstreams, in_arena, out_arena, recs, res, max_records, sres, nrecords, stream,
+                               opts);
 }
 
 extern "C" int tlsrec_stream_read(const tlsrec_stream_in_res *sres, uint32_t nstreams, const tlsrec_batch_rec *recs,
@@ -1953,12 +2132,16 @@ extern "C" int tlsrec_stream_read(const tlsrec_stream_in_res *sres, uint32_t nst
 }
 
 /* ---------------- DTLS host side ---------------------------------------- */
-extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in *conns, uint32_t nconns,
-                                   const tlsrec_dgram *dgrams, uint32_t ndgrams, uint8_t *arena,
-                                   tlsrec_batch_rec *recs, tlsrec_batch_res *res, int32_t *disp,
-                                   uint32_t max_records, tlsrec_dtls_in_res *cres, uint32_t *nrecords, void *stream)
+extern "C" int tlsrec_dtls_decrypt_ex(const tlsrec_keytab *kt, const tlsrec_dtls_in *conns, uint32_t nconns,
+                                      const tlsrec_dgram *dgrams, uint32_t ndgrams, uint8_t *arena,
+                                      tlsrec_batch_rec *recs, tlsrec_batch_res *res, int32_t *disp,
+                                      uint32_t max_records, tlsrec_dtls_in_res *cres, uint32_t *nrecords, void *stream,
+                                      const tlsrec_frame_opts *opts)
 {
     if (nrecords) *nrecords = 0;
+    bool cbc;
+    if (const int orc = frame_opts(opts, false, &cbc)) return orc;
+    cbc = cbc && tlsrec__keytab_has_cbc(kt);      /* (a table without CBC slots: the plain call's kernels) */
     if (!kt || (nconns && (!conns || !cres || (ndgrams && (!dgrams || !arena))))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (nconns == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
@@ -1987,9 +2170,10 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
          * headers again */
         const uint32_t per = nconns ? (uint32_t) ((ndgrams + nconns - 1) / nconns) : 0;
 #define TLSREC_DTLS_FRAME(S_) do { TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, S_, 0, 0, 0); \
-                           hipLaunchKernelGGL(dtls_frame_kernel<S_>, dim3(tiles), dim3(DG_THREADS), 0, st, conns, \
+                           with_cbc(cbc, [&](auto C) { \
+                           hipLaunchKernelGGL((dtls_frame_kernel<S_, C()>), dim3(tiles), dim3(DG_THREADS), 0, st, conns, \
                            nconns, dgrams, ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.bytes, \
-                           sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst); } while (0)
+                           sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst); }); } while (0)
         if (!env_flag("TLSREC_DTLS_STASH", true) || per > 16) TLSREC_DTLS_FRAME(0);
         else if (per > 4) TLSREC_DTLS_FRAME(16);
         else TLSREC_DTLS_FRAME(4);
@@ -1999,13 +2183,17 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
         else r = fetch_total(sc, nconns, st, &total, &avg);
     } else if (r == 0) {
         TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, -1, 0, 0, 0);
-        hipLaunchKernelGGL(dtls_count_kernel, dim3(blocks(nconns + 1, 256)), dim3(256), 0, st, conns, nconns, dgrams,
-                           ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.bytes);
+        with_cbc(cbc, [&](auto C) {
+            hipLaunchKernelGGL(dtls_count_kernel<C()>, dim3(blocks(nconns + 1, 256)), dim3(256), 0, st, conns, nconns,
+                               dgrams, ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.bytes);
+        });
         uint64_t seq = 0;
         r = hipGetLastError() == hipSuccess ? scan_publish(sc, nconns, st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         if (r == 0 && recs && res) {   /* emitted while the host collects the totals (as the stream path) */
-            hipLaunchKernelGGL(dtls_emit_kernel, dim3(blocks(nconns, 256)), dim3(256), 0, st, conns, nconns, dgrams,
-                               ndgrams, (const uint8_t *) arena, sc.offs, slots, cap, recs, max_records, res);
+            with_cbc(cbc, [&](auto C) {
+                hipLaunchKernelGGL(dtls_emit_kernel<C()>, dim3(blocks(nconns, 256)), dim3(256), 0, st, conns, nconns,
+                                   dgrams, ndgrams, (const uint8_t *) arena, sc.offs, slots, cap, recs, max_records, res);
+            });
             if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         }
         if (r == 0) r = collect_totals(sc, nconns, st, seq, &total, &avg);
@@ -2014,19 +2202,31 @@ extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in
     if (r == 0 && total && (!recs || !res || !disp)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (r == 0 && total)
         r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg,
-                                env_flag("TLSREC_RX_PREFILL", true));
+                                env_flag("TLSREC_RX_PREFILL", true), cbc);
     if (r == 0) {
-        if (fused)
-            hipLaunchKernelGGL(dtls_finish_kernel<true>, dim3(blocks(nconns, 256)), dim3(256), 0, st, conns, nconns,
-                               dgrams, ndgrams, arena, sc.offs, sc.counts, slots, cap, recs, res, disp, cres, dgst);
-        else
-            hipLaunchKernelGGL(dtls_finish_kernel<false>, dim3(blocks(nconns, 256)), dim3(256), 0, st, conns, nconns,
-                               dgrams, ndgrams, arena, sc.offs, sc.counts, slots, cap, recs, res, disp, cres,
-                               (const uint32_t *) nullptr);
+        with_cbc(cbc, [&](auto C) {
+            if (fused)
+                hipLaunchKernelGGL((dtls_finish_kernel<true, C()>), dim3(blocks(nconns, 256)), dim3(256), 0, st, conns,
+                                   nconns, dgrams, ndgrams, arena, sc.offs, sc.counts, slots, cap, recs, res, disp, cres,
+                                   dgst);
+            else
+                hipLaunchKernelGGL((dtls_finish_kernel<false, C()>), dim3(blocks(nconns, 256)), dim3(256), 0, st, conns,
+                                   nconns, dgrams, ndgrams, arena, sc.offs, sc.counts, slots, cap, recs, res, disp, cres,
+                                   (const uint32_t *) nullptr);
+        });
         if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     }
     if (dgl.mem) tlsrec__scratch_release(&dgl);
     tlsrec__scratch_release(&sc.lease);
     if (r == 0 && nrecords) *nrecords = total;
     return r;
+}
+
+extern "C" int tlsrec_dtls_decrypt(const tlsrec_keytab *kt, const tlsrec_dtls_in *conns, uint32_t nconns,
+                                   const tlsrec_dgram *dgrams, uint32_t ndgrams, uint8_t *arena,
+                                   tlsrec_batch_rec *recs, tlsrec_batch_res *res, int32_t *disp,
+                                   uint32_t max_records, tlsrec_dtls_in_res *cres, uint32_t *nrecords, void *stream)
+{
+    return tlsrec_dtls_decrypt_ex(kt, conns, nconns, dgrams, ndgrams, arena, recs, res, disp, max_records, cres,
+                                  nrecords, stream, nullptr);
 }

@@ -525,14 +525,25 @@ TLSREC_CBC_HD uint4 cbc_aes_decrypt(const uint8_t *lds, uint32_t lb, RK dkr, uin
 }
 
 /* ---------------- record sizes (host helpers, ssl_tls.c:7822-7835) ------- */
+/* explicit IV + ciphertext (+ MAC) of `inner` plaintext bytes -- the content,
+ * or with a connection ID the DTLSInnerPlaintext (ssl_msg.c:874-897) -- under
+ * a MAC of ml bytes (ssl_msg.c:906-968, :1080-1253).  The one place this
+ * arithmetic lives: cbc_record_len, the send frame kernels (stream.hip) and
+ * tlsrec_*_out_size_cbc. */
+template <typename T>
+TLSREC_CBC_HD T cbc_body_len(T ml, bool etm, T inner)
+{
+    const T body = inner + (etm ? (T) 0 : ml);
+    const T padded = (body + 16) & ~(T) 15;         /* 1..16 bytes of padding */
+    return 16 + padded + (etm ? ml : (T) 0);
+}
+
 /* explicit IV + ciphertext (+ MAC) of a record of content_len bytes */
 TLSREC_CBC_HD uint32_t cbc_record_len(int mac, int etm, uint32_t content_len)
 {
     const uint32_t ml = cbc_maclen(mac);
     if (ml == 0 || etm < 0 || etm > 1) return 0;
-    const uint32_t body = content_len + (etm ? 0u : ml);
-    const uint32_t padded = (body + 16) & ~15u;     /* 1..16 bytes of padding */
-    return 16 + padded + (etm ? ml : 0u);
+    return cbc_body_len<uint32_t>(ml, etm != 0, content_len);
 }
 
 } /* namespace tlsrec */

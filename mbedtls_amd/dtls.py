@@ -12,13 +12,45 @@ import ctypes
 
 from . import _abi
 from .batch import KeyTable, _ptr, _stream
-from .stream import StreamError, _dev
+from .stream import StreamError, _dev, _opts, frame_opts  # noqa: F401  (frame_opts: the _ex calls' options)
 
 DGRAM, DTLS_IN, DTLS_IN_RES = _abi.DGRAM, _abi.DTLS_IN, _abi.DTLS_IN_RES
 
 
 def out_size(cipher: int, granularity: int, cid_len: int, in_len: int, max_frag: int = 0) -> int:
     return int(_abi.load().tlsrec_dtls_out_size(cipher, granularity, cid_len, in_len, max_frag))
+
+
+def out_size_cbc(mac: int, etm: int, cid_len: int, in_len: int, max_frag: int = 0) -> int:
+    return int(_abi.load().tlsrec_dtls_out_size_cbc(mac, etm, cid_len, in_len, max_frag))
+
+
+def decrypt_ex(kt: KeyTable, conns, n: int, dgrams, ndgrams: int, arena, recs, res, disp, max_records: int, cres,
+               opts=None, stream=None) -> int:
+    """decrypt() with a tlsrec_frame_opts (frame_opts(); None = the plain call)."""
+    dev = arena.device if hasattr(arena, "device") else None
+    conns, dgrams = _dev(conns, dev), _dev(dgrams, dev)
+    total = ctypes.c_uint32()
+    r = _abi.load().tlsrec_dtls_decrypt_ex(kt.handle, _ptr(conns), n, _ptr(dgrams), ndgrams, _ptr(arena), _ptr(recs),
+                                           _ptr(res), _ptr(disp), max_records, _ptr(cres), ctypes.byref(total),
+                                           _stream(stream), _opts(opts))
+    if r != 0:
+        raise StreamError("tlsrec_dtls_decrypt_ex", r)
+    return total.value
+
+
+def encrypt_ex(kt: KeyTable, streams, n: int, in_arena, out_arena, recs, res, max_records: int, sres, opts=None,
+               stream=None) -> int:
+    """encrypt() with a tlsrec_frame_opts (frame_opts(cbc_ivs=...); None = the plain call)."""
+    dev = out_arena.device if hasattr(out_arena, "device") else None
+    streams = _dev(streams, dev)
+    total = ctypes.c_uint32()
+    r = _abi.load().tlsrec_dtls_encrypt_ex(kt.handle, _ptr(streams), n, _ptr(in_arena), _ptr(out_arena), _ptr(recs),
+                                           _ptr(res), max_records, _ptr(sres), ctypes.byref(total), _stream(stream),
+                                           _opts(opts))
+    if r != 0:
+        raise StreamError("tlsrec_dtls_encrypt_ex", r)
+    return total.value
 
 
 def decrypt(kt: KeyTable, conns, n: int, dgrams, ndgrams: int, arena, recs, res, disp, max_records: int, cres,

@@ -37,6 +37,48 @@ def out_size(tls_version: int, cipher: int, granularity: int, in_len: int, max_f
     return int(_abi.load().tlsrec_stream_out_size(tls_version, cipher, granularity, in_len, max_frag))
 
 
+def out_size_cbc(mac: int, etm: int, in_len: int, max_frag: int = 0) -> int:
+    return int(_abi.load().tlsrec_stream_out_size_cbc(mac, etm, in_len, max_frag))
+
+
+def frame_opts(flags: int = _abi.FRAME_CBC, cbc_ivs=None, reserved: int = 0):
+    """A tlsrec_frame_opts for the _ex calls: CBC slots usable; cbc_ivs (send):
+    a device buffer of 16 * max_records bytes, record j's explicit IV at 16 j."""
+    return _abi.CFrameOpts(flags, reserved, _ptr(cbc_ivs))
+
+
+def _opts(opts):
+    return ctypes.byref(opts) if opts is not None else None
+
+
+def decrypt_ex(kt: KeyTable, streams, n: int, arena, recs, res, max_records: int, sres, opts=None,
+               stream=None) -> int:
+    """decrypt() with a tlsrec_frame_opts (frame_opts(); None = the plain call)."""
+    dev = arena.device if hasattr(arena, "device") else None
+    streams = _dev(streams, dev)
+    total = ctypes.c_uint32()
+    r = _abi.load().tlsrec_stream_decrypt_ex(kt.handle, _ptr(streams), n, _ptr(arena), _ptr(recs), _ptr(res),
+                                             max_records, _ptr(sres), ctypes.byref(total), _stream(stream),
+                                             _opts(opts))
+    if r != 0:
+        raise StreamError("tlsrec_stream_decrypt_ex", r)
+    return total.value
+
+
+def encrypt_ex(kt: KeyTable, streams, n: int, in_arena, out_arena, recs, res, max_records: int, sres, opts=None,
+               stream=None) -> int:
+    """encrypt() with a tlsrec_frame_opts (frame_opts(cbc_ivs=...); None = the plain call)."""
+    dev = out_arena.device if hasattr(out_arena, "device") else None
+    streams = _dev(streams, dev)
+    total = ctypes.c_uint32()
+    r = _abi.load().tlsrec_stream_encrypt_ex(kt.handle, _ptr(streams), n, _ptr(in_arena), _ptr(out_arena),
+                                             _ptr(recs), _ptr(res), max_records, _ptr(sres), ctypes.byref(total),
+                                             _stream(stream), _opts(opts))
+    if r != 0:
+        raise StreamError("tlsrec_stream_encrypt_ex", r)
+    return total.value
+
+
 def decrypt(kt: KeyTable, streams, n: int, arena, recs, res, max_records: int, sres, stream=None) -> int:
     """Returns the number of records framed; per-connection results land in
     `sres` (STREAM_IN_RES), per-record ones in `recs` / `res`."""

@@ -6,6 +6,7 @@ gets the record streams the send side produced (checked against the oracle
 on a sample of connections).  Prints one JSON line per direction.
 
     python tools/bench_stream.py [--conns 65536] [--recs 16] [--content 16384] [--cipher 2]
+    python tools/bench_stream.py --cbc --content 1400     # the framed AES-CBC + HMAC rows (tools/cbc_rows.py)
 """
 import argparse
 import json
@@ -28,7 +29,13 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="wall-time target of each CPU leg's sample")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cbc", action="store_true",
+                    help="the AES-128-CBC + HMAC-SHA256 rows instead (both MAC orders, the framed calls against "
+                         "the same-run batch call: tools/cbc_rows.py)")
     a = ap.parse_args()
+    if a.cbc:
+        from tools import cbc_rows
+        return cbc_rows.run(a, dtls=False)
     from tools import rowlib
     import torch
     import mbedtls_amd as M

@@ -487,10 +487,12 @@ int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count
  * tlsrec_stream_* / tlsrec_dtls_* calls treat a CBC slot as a slot that was
  * never loaded.
  *
+ * Batch key derivation for these suites is tlsrec_tls12_keytab_derive_cbc
+ * (below).
+ *
  * Out of scope: session tickets and the single-record server
  * (tlsrec_encrypt_buf / _decrypt_buf) treat a CBC slot as a slot that was
- * never loaded; ARIA-CBC, Camellia-CBC and the NULL
- * cipher; batch key derivation (tlsrec_tls12_keytab_derive) for CBC suites.
+ * never loaded; ARIA-CBC, Camellia-CBC and the NULL cipher.
  * tlsrec_keytab_load, tlsrec_transform_setup, tlsrec_tls12_split_key_block,
  * tlsrec_tls12_make_keys, tlsrec_tls12_keytab_derive, tlsrec_tls13_keytab_derive, tlsrec_stream_out_size
  * and tlsrec_dtls_out_size answer ids 23 and 24 as unknown ciphers. */
@@ -541,6 +543,29 @@ int tlsrec_tls12_split_key_block_cbc(int cipher, int mac, const unsigned char *k
  * tlsrec_tls12_make_keys). */
 int tlsrec_tls12_make_keys_cbc(int prf, int cipher, int mac, const unsigned char master[48],
                                const unsigned char randbytes[64], tlsrec_cbc_key_set *out);
+
+/* tlsrec_tls12_keytab_derive for the CBC + HMAC suites: for each of `count`
+ * connections run PRF(master, "key expansion", randbytes) for 2 * maclen +
+ * 2 * key_len bytes on the GPU, split it as tlsrec_tls12_split_key_block_cbc
+ * does and load client_write into slot first + 2*i and server_write into slot
+ * first + 2*i + 1 as tlsrec_keytab_load_cbc loads them (tls_minor 3, `mac`,
+ * `etm`).  `etm` (0 = MAC-then-encrypt, 1 = encrypt-then-MAC) holds for the
+ * whole call: group connections by the negotiated extension.  `conns` is
+ * device memory and only read.  Asynchronous on `stream`: no host
+ * synchronisation, and no key material reaches the host; the derived records
+ * pass through a device staging area of the table (capacity x 128 bytes,
+ * allocated by the first call, freed with the table), which is zeroized on
+ * `stream` right after the key setup.  A (re)loaded slot has no connection ID.
+ * Every (cipher, mac, prf) combination is accepted, as tlsrec_tls12_make_keys_cbc
+ * accepts them.  Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for kt
+ * NULL, conns NULL with count != 0, or [first, first + 2*count) overflowing or
+ * running past the table; TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for an unknown
+ * cipher or mac, then for an unknown prf; TLSREC_ERR_SSL_BAD_INPUT_DATA for etm
+ * other than 0 or 1.  count == 0 with valid arguments returns 0 and launches
+ * nothing. */
+int tlsrec_tls12_keytab_derive_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count,
+                                   int cipher, int mac, int etm, int prf,
+                                   const tlsrec_tls12_conn *conns, void *stream);
 
 /* ---- TLS stream record layer --------------------------
  * Whole-connection framing on the device: received byte streams are split at

@@ -206,6 +206,7 @@ SIGNATURES = {
     "tlsrec_cbc_minlen": (_U32, [_INT, _INT]),
     "tlsrec_tls12_split_key_block_cbc": (_INT, [_INT, _INT, _VP, _SZ, _VP]),
     "tlsrec_tls12_make_keys_cbc": (_INT, [_INT, _INT, _INT, _VP, _VP, _VP]),
+    "tlsrec_tls12_keytab_derive_cbc": (_INT, [_VP, _U32, _U32, _INT, _INT, _INT, _INT, _VP, _VP]),
     "tlsrec_version_string": (ctypes.c_char_p, []),
 }
 

@@ -33,6 +33,7 @@ struct tlsrec_keytab {
     uint8_t *d_cipher;        /* each slot's cipher, one byte (the bucket pass reads it per record:
                                  an L2-resident array instead of a line of the 1 KiB slot) */
     tlsrec_key_material *d_stage;
+    tlsrec_cbc_key_material *d_stage_cbc;   /* capacity records, made by the first CBC batch derivation */
     uint8_t *h_cipher;        /* host mirror of each slot's cipher */
     uint32_t cipher_mask;     /* 1 << TLSREC_CIPHER_* of every loaded slot */
     uint32_t nloaded;         /* slots holding a key */
@@ -139,6 +140,7 @@ extern "C" void tlsrec_keytab_free(tlsrec_keytab *kt)
         hipMemset(kt->d_slots, 0, sizeof(SlotState) * (size_t) kt->capacity);
         hipMemset(kt->d_ghtab, 0, sizeof(uint4) * (size_t) KEY_TABLE_WORDS * kt->capacity);
         if (kt->d_dummy) hipMemset(kt->d_dummy, 0, GCM_DUMMY_BYTES);   /* idle lanes' keystream under the keys */
+        if (kt->d_stage_cbc) hipMemset(kt->d_stage_cbc, 0, sizeof(tlsrec_cbc_key_material) * (size_t) kt->capacity);
         hipDeviceSynchronize();
     }
     hipFree(kt->d_dummy);
@@ -146,6 +148,7 @@ extern "C" void tlsrec_keytab_free(tlsrec_keytab *kt)
     hipFree(kt->d_ghtab);
     hipFree(kt->d_cipher);
     hipFree(kt->d_stage);
+    hipFree(kt->d_stage_cbc);
     free(kt->h_cipher);
     free(kt);
 }
@@ -320,6 +323,38 @@ extern "C" int tlsrec__keytab_commit_staged(tlsrec_keytab *kt, uint32_t first, u
     }
     kt->cipher_mask |= 1u << cipher;
     return hip_ok(tlsrec__launch_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, kt->d_stage + first, first, count, st));
+}
+
+/* The same for CBC + HMAC material (tlsrec_tls12_keytab_derive_cbc): 128-byte
+ * records, so a staging area of their own, allocated by the first call that
+ * needs it (a table of AEAD slots only never pays for it); NULL = no memory. */
+extern "C" tlsrec_cbc_key_material *tlsrec__keytab_stage_cbc(tlsrec_keytab *kt)
+{
+    if (!kt->d_stage_cbc &&
+        hipMalloc((void **) &kt->d_stage_cbc, sizeof(tlsrec_cbc_key_material) * (size_t) kt->capacity) != hipSuccess)
+        kt->d_stage_cbc = NULL;
+    return kt->d_stage_cbc;
+}
+
+/* What tlsrec_keytab_load_cbc does after its checks, for `count` staged
+ * records of one (cipher, mac, etm); then the staged range, which holds raw
+ * MAC keys, is zeroized behind the key setup on the same stream (no wait). */
+extern "C" int tlsrec__keytab_commit_staged_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int mac,
+                                                int etm, hipStream_t st)
+{
+    if (!kt->d_stage_cbc) return TLSREC_ERR_SSL_INTERNAL_ERROR;
+    for (uint32_t i = 0; i < count; i++) {
+        if (kt->h_cipher[first + i] == 0) kt->nloaded++;
+        kt->h_cipher[first + i] = (uint8_t) cipher;
+    }
+    kt->cipher_mask |= 1u << cipher;
+    kt->cbc_variants |= 1u << (3 * (cipher - TLSREC_CIPHER_CBC_FIRST) + (mac - 1));
+    kt->cbc_etm |= 1u << etm;
+    tlsrec_cbc_key_material *src = kt->d_stage_cbc + first;
+    int r = hip_ok(tlsrec__launch_cbc_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, src, first, count, st));
+    if (hipMemsetAsync(src, 0, sizeof(*src) * (size_t) count, st) != hipSuccess && r == 0)
+        r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    return r;
 }
 
 /* waves per GCM workgroup: 16 (default) or 8; TLSREC_GCM_WAVES overrides */

@@ -382,7 +382,8 @@ __global__ void __launch_bounds__(64) tls13_derive_kernel(DeriveArgs a)
 /* ---------------- TLS 1.2 batch key expansion ---------------------------
  * PRF(master, "key expansion", server_random || client_random) for one
  * connection per lane.  Every shape is fixed (48-byte key, 77-byte seed, at
- * most 88 bytes out), so nothing here goes through Hash / put(): the message
+ * most 88 bytes out for an AEAD suite and 160 for a CBC + HMAC one), so
+ * nothing here goes through Hash / put(): the message
  * blocks are assembled as big-endian words with their padding and length
  * words as constants, the compression works on a 16-word window and 8 state
  * words held in registers, and the two HMAC midstates (key ^ ipad, key ^
@@ -470,11 +471,13 @@ __device__ __forceinline__ void tls12_seed_words(const uint32_t (&R)[16], uint32
     S[19] = (R[15] << 24) | 0x00800000u;
 }
 
-/* P_SHA256: KB receives 8 words per iteration, ITERS = ceil(out_len / 32) */
-template <int ITERS>
+/* P_SHA256: KB (KBW words, the key block of the caller's shape) receives 8
+ * words per iteration, ITERS = ceil(out_len / 32) */
+template <int ITERS, int KBW>
 __device__ __forceinline__ void tls12_expand_sha256(const uint32_t (&M)[12], const uint32_t (&R)[16],
-                                                    uint32_t (&KB)[24])
+                                                    uint32_t (&KB)[KBW])
 {
+    static_assert(ITERS * 8 <= KBW, "key block holds every iteration's digest");
     const uint32_t iv[8] = { 0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
                              0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u };
     const uint32_t HMAC_LEN = (64 + 32) * 8;     /* bits of key block || 32-byte digest */
@@ -560,10 +563,11 @@ __device__ __forceinline__ void tls12_expand_sha256(const uint32_t (&M)[12], con
 
 /* P_SHA384 (SHA-512 compression, 128-byte blocks, 48-byte digests): KB
  * receives 12 words per iteration, ITERS = ceil(out_len / 48) */
-template <int ITERS>
+template <int ITERS, int KBW>
 __device__ __forceinline__ void tls12_expand_sha384(const uint32_t (&M)[12], const uint32_t (&R)[16],
-                                                    uint32_t (&KB)[24])
+                                                    uint32_t (&KB)[KBW])
 {
+    static_assert(ITERS * 12 <= KBW, "key block holds every iteration's digest");
     const uint64_t iv[8] = { 0xcbbb9d5dc1059ed8ULL, 0x629a292a367cd507ULL, 0x9159015a3070dd17ULL,
                              0x152fecd8f70e5939ULL, 0x67332667ffc00b31ULL, 0x8eb44a8768581511ULL,
                              0xdb0c2e0d64f98fa7ULL, 0x47b5481dbefa4fa4ULL };
@@ -660,24 +664,12 @@ __device__ __forceinline__ void tls12_expand_sha384(const uint32_t (&M)[12], con
     for (int j = 0; j < 20; j++) S[j] = 0;
 }
 
-struct Tls12Args {
-    const tlsrec_tls12_conn *conns;
-    tlsrec_key_material *out;     /* staging area of slot `first`: 2 records per connection */
-    uint32_t count, cipher, taglen, aligned;
-};
-
-/* One lane per connection; KL / IVL = the cipher's key length and TLS 1.2
- * fixed_ivlen, so the split of the key block (ssl_tls.c:7858-7892) indexes
- * registers with constants. */
-template <int ALG, int KL, int IVL> __global__ void __launch_bounds__(64) tls12_derive_kernel(Tls12Args a)
+/* One connection's master secret and random bytes as big-endian words: seven
+ * 16-byte loads, or bytes when the array is not 16-byte aligned. */
+__device__ __forceinline__ void tls12_load_conn(const tlsrec_tls12_conn *conn, bool aligned, uint32_t (&M)[12],
+                                                uint32_t (&R)[16])
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.count) return;
-    constexpr int OUT = 2 * KL + 2 * IVL, H = ALG == H_SHA384 ? 48 : 32, ITERS = (OUT + H - 1) / H;
-    static_assert(ITERS * H <= 96 && KL % 4 == 0 && IVL % 4 == 0, "key block shape");
-    const uint8_t *c = reinterpret_cast<const uint8_t *>(a.conns + i);
-    const bool aligned = a.aligned != 0;
-    uint32_t M[12], R[16], KB[24];
+    const uint8_t *c = reinterpret_cast<const uint8_t *>(conn);
     if (aligned) {
         const uint4 *q = reinterpret_cast<const uint4 *>(c);
 #pragma unroll
@@ -697,6 +689,25 @@ template <int ALG, int KL, int IVL> __global__ void __launch_bounds__(64) tls12_
 #pragma unroll
         for (int n = 0; n < 16; n++) R[n] = load_be32(c + 48 + 4 * n, false);
     }
+}
+
+struct Tls12Args {
+    const tlsrec_tls12_conn *conns;
+    tlsrec_key_material *out;     /* staging area of slot `first`: 2 records per connection */
+    uint32_t count, cipher, taglen, aligned;
+};
+
+/* One lane per connection; KL / IVL = the cipher's key length and TLS 1.2
+ * fixed_ivlen, so the split of the key block (ssl_tls.c:7858-7892) indexes
+ * registers with constants. */
+template <int ALG, int KL, int IVL> __global__ void __launch_bounds__(64) tls12_derive_kernel(Tls12Args a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    constexpr int OUT = 2 * KL + 2 * IVL, H = ALG == H_SHA384 ? 48 : 32, ITERS = (OUT + H - 1) / H;
+    static_assert(ITERS * H <= 96 && KL % 4 == 0 && IVL % 4 == 0, "key block shape");
+    uint32_t M[12], R[16], KB[24];
+    tls12_load_conn(a.conns + i, a.aligned != 0, M, R);
 #pragma unroll
     for (int j = 0; j < 24; j++) KB[j] = 0;
     if constexpr (ALG == H_SHA384) tls12_expand_sha384<ITERS>(M, R, KB);
@@ -722,6 +733,56 @@ template <int ALG, int KL, int IVL> __global__ void __launch_bounds__(64) tls12_
     }
 #pragma unroll
     for (int j = 0; j < 24; j++) KB[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 12; j++) M[j] = 0;
+}
+
+struct Tls12CbcArgs {
+    const tlsrec_tls12_conn *conns;
+    tlsrec_cbc_key_material *out;     /* CBC staging area of slot `first`: 2 records per connection */
+    uint32_t count, head, aligned;    /* head: cipher | tls_minor 3 | mac | etm, the first word of a record */
+};
+
+/* The CBC + HMAC suites: the key block is client_mac | server_mac | client_key
+ * | server_key (ssl_tls.c:7858-7886, mac_key_len != 0; TLS 1.2 carries the CBC
+ * IV in each record, so no IV is derived), 72 to 160 bytes = 3 to 5 P_SHA256 or
+ * 2 to 4 P_SHA384 iterations.  One lane per connection as above; KL / ML = the
+ * key and MAC key lengths, all multiples of 4 bytes, so the split indexes
+ * registers with constants.  Each side is one tlsrec_cbc_key_material (128
+ * bytes: head, 44 reserved bytes, key at byte 48, mac_key at byte 80). */
+template <int ALG, int KL, int ML> __global__ void __launch_bounds__(64) tls12_derive_cbc_kernel(Tls12CbcArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    constexpr int OUT = 2 * ML + 2 * KL, H = ALG == H_SHA384 ? 48 : 32, ITERS = (OUT + H - 1) / H;
+    constexpr int KBW = ITERS * H / 4;
+    static_assert(KL % 4 == 0 && KL <= 32 && ML % 4 == 0 && ML <= 48, "key block shape");
+    static_assert(sizeof(tlsrec_cbc_key_material) == 128 && offsetof(tlsrec_cbc_key_material, key) == 48 &&
+                  offsetof(tlsrec_cbc_key_material, mac_key) == 80, "tlsrec_cbc_key_material layout");
+    uint32_t M[12], R[16], KB[KBW];
+    tls12_load_conn(a.conns + i, a.aligned != 0, M, R);
+#pragma unroll
+    for (int j = 0; j < KBW; j++) KB[j] = 0;
+    if constexpr (ALG == H_SHA384) tls12_expand_sha384<ITERS>(M, R, KB);
+    else tls12_expand_sha256<ITERS>(M, R, KB);
+    uint4 *dst = reinterpret_cast<uint4 *>(a.out + 2 * (size_t) i);
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+        uint32_t km[32];
+        km[0] = a.head;
+#pragma unroll
+        for (int j = 1; j < 32; j++) km[j] = 0;
+#pragma unroll
+        for (int j = 0; j < KL / 4; j++) km[12 + j] = __builtin_bswap32(KB[2 * ML / 4 + side * (KL / 4) + j]);
+#pragma unroll
+        for (int j = 0; j < ML / 4; j++) km[20 + j] = __builtin_bswap32(KB[side * (ML / 4) + j]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) dst[8 * side + k] = make_uint4(km[4 * k], km[4 * k + 1], km[4 * k + 2], km[4 * k + 3]);
+#pragma unroll
+        for (int j = 0; j < 32; j++) km[j] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < KBW; j++) KB[j] = 0;
 #pragma unroll
     for (int j = 0; j < 12; j++) M[j] = 0;
 }
@@ -1098,7 +1159,7 @@ extern "C" int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uin
  *   key-block split                   :7858-7892     tlsrec_tls12_split_key_block (host only)
  *   tls_prf(.., "key expansion", ..)  :7750          tlsrec_tls12_make_keys
  *   mbedtls_ssl_tls12_export_keying_material :8886   tlsrec_tls12_export_keying_material
- *   (batch)                                          tlsrec_tls12_keytab_derive
+ *   (batch)                                          tlsrec_tls12_keytab_derive, _derive_cbc
  * ==================================================================== */
 static int prf_index(int prf)
 {
@@ -1320,5 +1381,62 @@ extern "C" int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uin
 {
     int r = tlsrec__tls12_stage_keys(kt, first, count, cipher, prf, conns, stream);
     if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, 2 * count, cipher, (hipStream_t) stream);
+    return r;
+}
+
+/* ---- the same for the CBC + HMAC suites ---- */
+extern "C" tlsrec_cbc_key_material *tlsrec__keytab_stage_cbc(tlsrec_keytab *kt);
+extern "C" int tlsrec__keytab_commit_staged_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int mac,
+                                                int etm, hipStream_t st);
+
+template <int ALG, int KL, int ML> static hipError_t tls12_launch_cbc(const Tls12CbcArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL((tls12_derive_cbc_kernel<ALG, KL, ML>), dim3((a.count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+template <int ALG, int KL> static hipError_t tls12_launch_cbc_mac(size_t ml, const Tls12CbcArgs &a, hipStream_t st)
+{
+    return ml == 20 ? tls12_launch_cbc<ALG, KL, 20>(a, st)
+           : ml == 32 ? tls12_launch_cbc<ALG, KL, 32>(a, st) : tls12_launch_cbc<ALG, KL, 48>(a, st);
+}
+
+/* The derive kernel alone: 2 * count tlsrec_cbc_key_material records into the
+ * table's CBC staging area, nothing committed (see tlsrec__tls13_stage_keys). */
+extern "C" int tlsrec__tls12_stage_keys_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int mac,
+                                            int etm, int prf, const tlsrec_tls12_conn *conns, void *stream)
+{
+    if (!kt || (!conns && count)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const uint32_t cap = tlsrec_keytab_capacity(kt);
+    if (first > cap || (uint64_t) count * 2 > (uint64_t) (cap - first)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
+    if (kl == 0 || ml == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    const int alg = prf_index(prf);
+    if (alg < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (etm < 0 || etm > 1) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (count == 0) return 0;
+    tlsrec_cbc_key_material *stage = tlsrec__keytab_stage_cbc(kt);
+    if (!stage) return TLSREC_ERR_SSL_ALLOC_FAILED;
+    Tls12CbcArgs a;
+    a.conns = conns;
+    a.out = stage + first;
+    a.count = count;
+    a.head = (uint32_t) cipher | (3u << 8) | ((uint32_t) mac << 16) | ((uint32_t) etm << 24);
+    a.aligned = ((uintptr_t) conns & 15) == 0;
+    hipStream_t st = (hipStream_t) stream;
+    hipError_t e;
+    if (alg == H_SHA384)
+        e = kl == 16 ? tls12_launch_cbc_mac<H_SHA384, 16>(ml, a, st) : tls12_launch_cbc_mac<H_SHA384, 32>(ml, a, st);
+    else
+        e = kl == 16 ? tls12_launch_cbc_mac<H_SHA256, 16>(ml, a, st) : tls12_launch_cbc_mac<H_SHA256, 32>(ml, a, st);
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls12_keytab_derive_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int mac,
+                                              int etm, int prf, const tlsrec_tls12_conn *conns, void *stream)
+{
+    int r = tlsrec__tls12_stage_keys_cbc(kt, first, count, cipher, mac, etm, prf, conns, stream);
+    if (r == 0 && count)
+        r = tlsrec__keytab_commit_staged_cbc(kt, first, 2 * count, cipher, mac, etm, (hipStream_t) stream);
     return r;
 }

@@ -8,6 +8,7 @@ reference functions; the PRF (RFC 5246 section 5) runs in HIP kernels.
     tls_prf(.., "key expansion", ..) + split  (:7750)  -> tls12_make_keys
     mbedtls_ssl_tls12_export_keying_material  (:8886)  -> tls12_export_keying_material
     batch: master secrets in HBM -> key-table slots    -> tls12_keytab_derive
+    the same for the AES-CBC + HMAC suites             -> tls12_keytab_derive_cbc
 
 `prf` is explicit (TLS 1.2 fixes the hash per suite, not per cipher); errors
 raise KeyScheduleError with the reference's code.
@@ -29,7 +30,7 @@ CONN_BYTES = ctypes.sizeof(_abi.CTls12Conn)      # master[48] || server_random[3
 
 __all__ = ["PRF_NONE", "PRF_SHA384", "PRF_SHA256", "IS_CLIENT", "IS_SERVER", "CONN_BYTES", "KeyScheduleError",
            "tls_prf", "tls12_compute_master", "tls12_split_key_block", "tls12_make_keys",
-           "tls12_export_keying_material", "tls12_keytab_derive", "tls12_slots"]
+           "tls12_export_keying_material", "tls12_keytab_derive", "tls12_keytab_derive_cbc", "tls12_slots"]
 
 
 def _key_set(ks):
@@ -93,6 +94,15 @@ def tls12_keytab_derive(kt: KeyTable, first: int, count: int, cipher: int, prf: 
     slot first + 2*i, its server_write key in slot first + 2*i + 1."""
     _chk("tlsrec_tls12_keytab_derive", _abi.load().tlsrec_tls12_keytab_derive(
         kt.handle if kt is not None else None, first, count, cipher, prf, _ptr(conns), _stream(stream)))
+
+
+def tls12_keytab_derive_cbc(kt: KeyTable, first: int, count: int, cipher: int, mac: int, etm: int, prf: int, conns,
+                            stream=None) -> None:
+    """tls12_keytab_derive for an AES-CBC + HMAC suite (mbedtls_amd.cbc ids):
+    the same `conns` and slot numbering; `etm` (0 / 1, encrypt-then-MAC) holds
+    for every connection of the call."""
+    _chk("tlsrec_tls12_keytab_derive_cbc", _abi.load().tlsrec_tls12_keytab_derive_cbc(
+        kt.handle if kt is not None else None, first, count, cipher, mac, etm, prf, _ptr(conns), _stream(stream)))
 
 
 def tls12_slots(first: int, i: int, endpoint: int):

@@ -12,11 +12,22 @@ tlsrec_tls13_keytab_derive (no KeyUpdate) for the same number of slots, and a
 CPU leg: OpenSSL EVP_KDF "TLS1-PRF" on the host's cores followed by
 tlsrec_keytab_load of the result (what a caller without the batch has to do).
 
+--tls12 --cbc-mac {1,2,3} [--etm]: the AES-CBC + HMAC suites
+(tlsrec_tls12_keytab_derive_cbc) at the suite shape of the MAC -- 1: AES-128-CBC
+SHA-1 with PRF SHA-256, 2: AES-128-CBC SHA-256 with PRF SHA-256, 3: AES-256-CBC
+SHA-384 with PRF SHA-384 (--cipher 23|24 and --prf override).  One run times
+(a) the call, (b) its derive kernel alone, (c) the host path it replaces --
+tlsrec_tls12_make_keys_cbc per connection, then one tlsrec_keytab_load_cbc --
+on a sample of at most 2 048 connections, and (d) tlsrec_tls12_keytab_derive
+for AES-128-GCM over the same connections as the yardstick, and states the
+derive kernels' cost per SHA-2 compression (DESIGN 3.5's 5n + 3 / 5n + 2).
+
 Prints one JSON line; the whole call and the derive kernel alone are timed
 with HIP events on the call's stream, the key-setup kernel is the difference.
 
     python tools/bench_keysched.py [--count 65536] [--cipher 2] [--steps 5]
     python tools/bench_keysched.py --tls12 [--prf sha256|sha384] [--count 65536] [--cipher 1]
+    python tools/bench_keysched.py --tls12 --cbc-mac 2 [--etm] [--count 65536]
 """
 import argparse
 import ctypes
@@ -145,17 +156,147 @@ def main_tls12(a):
         "cpu_baseline": cpu}))
 
 
+def _compressions(hname, out_len):
+    """SHA-2 compressions of one connection's key expansion: 5n + 3 (SHA-256), 5n + 2 (SHA-384)"""
+    h, extra = (48, 2) if hname == "sha384" else (32, 3)
+    return 5 * ((out_len + h - 1) // h) + extra
+
+
+def host_cbc_leg(prf, cipher, mac, etm, raw, sample):
+    """The path without the batch: tlsrec_tls12_make_keys_cbc per connection (a
+    synchronised single-shot PRF job each, the keys returned to the host), then
+    one tlsrec_keytab_load_cbc of the 2 * sample records."""
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import cbc as C
+    kt = M.KeyTable(2 * sample)
+    C.make_keys(prf, cipher, mac, raw[:48], raw[48:112])          # the control-path stream and arena exist
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    parts = []
+    for i in range(sample):
+        st, cw, sw = C.make_keys(prf, cipher, mac, raw[112 * i:112 * i + 48], raw[112 * i + 48:112 * i + 112])
+        assert st == 0, st
+        parts += [cw, sw]
+    keys = np.concatenate(parts)
+    keys["etm"] = etm
+    make_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    C.load(kt, keys)
+    torch.cuda.synchronize()
+    load_s = time.perf_counter() - t0
+    kt.close()
+    tot = make_s + load_s
+    return {"value": round(sample / tot), "unit": "connections/s", "sample_connections": sample,
+            "us_per_connection": round(tot / sample * 1e6, 2), "make_keys_seconds": round(make_s, 4),
+            "keytab_load_cbc_seconds": round(load_s, 4),
+            "what": "tlsrec_tls12_make_keys_cbc per connection (one synchronised PRF job each, keys to the host), "
+                    "then one tlsrec_keytab_load_cbc (keys back to the device + key setup); wall time"}
+
+
+def main_tls12_cbc(a):
+    from tools import rowlib
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import cbc as C
+    from mbedtls_amd import tls12 as T
+    from mbedtls_amd.batch import _ptr, _stream
+    from tests.prng import prng_array
+    dev = torch.device("cuda")
+    L = M.load()
+    vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+    L.tlsrec__tls12_stage_keys.restype = ci
+    L.tlsrec__tls12_stage_keys.argtypes = [vp, u32, u32, ci, ci, vp, vp]
+    L.tlsrec__tls12_stage_keys_cbc.restype = ci
+    L.tlsrec__tls12_stage_keys_cbc.argtypes = [vp, u32, u32, ci, ci, ci, ci, vp, vp]
+    mac, etm = a.cbc_mac, int(a.etm)
+    cipher = a.cipher if a.cipher is not None else (C.CIPHER_AES_256_CBC if mac == C.MAC_SHA384 else C.CIPHER_AES_128_CBC)
+    hname = a.prf or ("sha384" if mac == C.MAC_SHA384 else "sha256")
+    prfs = {"sha256": T.PRF_SHA256, "sha384": T.PRF_SHA384}
+    prf, gcm = prfs[hname], M.CIPHER_AES_128_GCM
+    n, nslots = a.count, 2 * a.count
+    raw = prng_array(0x7152, n * 112)
+    conns = torch.from_numpy(raw).to(dev)
+    kt, kt_gcm = M.KeyTable(nslots), M.KeyTable(nslots)     # a table each: no reload wipes in the timed calls
+
+    def ok(r):
+        assert r == 0, r
+
+    # the derive kernel alone leaves raw keys staged; the call that follows it zeroizes the range
+    legs = {
+        "cbc_derive_kernel": lambda: ok(L.tlsrec__tls12_stage_keys_cbc(kt.handle, 0, n, cipher, mac, etm, prf,
+                                                                        _ptr(conns), _stream(None))),
+        "cbc_call": lambda: T.tls12_keytab_derive_cbc(kt, 0, n, cipher, mac, etm, prf, conns),
+        "gcm_derive_kernel": lambda: ok(L.tlsrec__tls12_stage_keys(kt_gcm.handle, 0, n, gcm, T.PRF_SHA256, _ptr(conns),
+                                                                   _stream(None))),
+        "gcm_call": lambda: T.tls12_keytab_derive(kt_gcm, 0, n, gcm, T.PRF_SHA256, conns),
+    }
+    if hname == "sha384":       # the AEAD kernel under the same hash: SHA-512 compressions against SHA-512 ones
+        legs["gcm384_derive_kernel"] = lambda: ok(L.tlsrec__tls12_stage_keys(kt_gcm.handle, 0, n, gcm, T.PRF_SHA384,
+                                                                             _ptr(conns), _stream(None)))
+    ms, wall = {}, {}
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()
+        ms[name], wall[name] = rowlib.event_timed(fn, a.steps)
+    legs["gcm_call"]()          # (the SHA-384 kernel leg staged keys the table never took)
+    torch.cuda.synchronize()
+    kl, ml = C.CBC_KEYLEN[cipher], C.MACLEN[mac]
+    out_len = 2 * ml + 2 * kl
+    comp = {"cbc": _compressions(hname, out_len), "gcm": _compressions("sha256", 40), "gcm384": _compressions("sha384", 40)}
+    ns = {k: ms[k + "_derive_kernel"] * 1e6 / n / comp[k] for k in comp if k + "_derive_kernel" in ms}
+    has384 = "gcm384" in ns
+    host = None if a.no_cpu else host_cbc_leg(prf, cipher, mac, etm, raw.tobytes(), min(2048, n))
+    call_cps = n / (ms["cbc_call"] / 1e3)
+    print(json.dumps({
+        "metric": "TLS 1.2 CBC + HMAC key expansions into the key table per second", "value": round(call_cps),
+        "unit": "connections/s", "count": n, "slots": nslots, "cipher": cipher, "mac": mac, "etm": etm, "prf": hname,
+        "key_block_bytes": out_len, "compressions_per_connection": comp["cbc"],
+        "ms_per_batch_events": round(ms["cbc_call"], 4), "ms_per_batch_wall": round(wall["cbc_call"] * 1e3, 4),
+        "derive_kernel_ms": round(ms["cbc_derive_kernel"], 4),
+        "key_setup_and_wipe_ms": round(ms["cbc_call"] - ms["cbc_derive_kernel"], 4),
+        "key_setup_share_of_call": round(1 - ms["cbc_derive_kernel"] / ms["cbc_call"], 4),
+        "derive_kernel_ns_per_connection": round(ms["cbc_derive_kernel"] * 1e6 / n, 3),
+        "derive_kernel_ns_per_compression": round(ns["cbc"], 4),
+        "aes128gcm_same_run": {"prf": "sha256", "connections_per_s": round(n / (ms["gcm_call"] / 1e3)),
+                               "ms_per_batch_events": round(ms["gcm_call"], 4),
+                               "derive_kernel_ms": round(ms["gcm_derive_kernel"], 4),
+                               "key_setup_ms": round(ms["gcm_call"] - ms["gcm_derive_kernel"], 4),
+                               "compressions_per_connection": comp["gcm"],
+                               "derive_kernel_ns_per_compression": round(ns["gcm"], 4),
+                               "prf_sha384_derive_kernel_ms": round(ms["gcm384_derive_kernel"], 4) if has384 else None,
+                               "prf_sha384_compressions_per_connection": comp["gcm384"] if has384 else None,
+                               "prf_sha384_derive_kernel_ns_per_compression": round(ns["gcm384"], 4) if has384 else None},
+        "per_compression_vs_aead_kernel_same_hash": round(ns["cbc"] / ns["gcm384" if hname == "sha384" else "gcm"], 3),
+        "per_compression_vs_aes128gcm_sha256": round(ns["cbc"] / ns["gcm"], 3),
+        "host_path": host,
+        "speedup_vs_host_path": round(call_cps / host["value"], 1) if host else None,
+        "roofline": rowlib.roofline((112 + out_len) * n, ms["cbc_call"], "per connection: the 112-byte tlsrec_tls12_conn "
+                                    "read + the key block (2 * (maclen + key_len)); the key-table slots the key setup "
+                                    "builds are not counted", "tls12 cbc derive + cbc key setup + staging wipe")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--count", type=int, default=65536)
-    ap.add_argument("--cipher", type=int, default=2)
+    ap.add_argument("--cipher", type=int, default=None, help="default 2 (with --cbc-mac: the suite's, 23 or 24)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--update", type=int, default=1)
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="wall-time target of the CPU sample")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--tls12", action="store_true", help="the TLS 1.2 key expansion (tlsrec_tls12_keytab_derive)")
-    ap.add_argument("--prf", choices=["sha256", "sha384"], default="sha256", help="--tls12: the suite's PRF hash")
+    ap.add_argument("--prf", choices=["sha256", "sha384"], default=None,
+                    help="--tls12: the suite's PRF hash (default sha256; with --cbc-mac 3 sha384)")
+    ap.add_argument("--cbc-mac", type=int, choices=[1, 2, 3], default=0,
+                    help="--tls12: an AES-CBC + HMAC suite (1 SHA-1, 2 SHA-256, 3 SHA-384), tlsrec_tls12_keytab_derive_cbc")
+    ap.add_argument("--etm", action="store_true", help="--cbc-mac: encrypt-then-MAC slots")
     a = ap.parse_args()
+    if a.cbc_mac:
+        if not a.tls12:
+            ap.error("--cbc-mac goes with --tls12")
+        return main_tls12_cbc(a)
+    a.cipher = 2 if a.cipher is None else a.cipher
+    a.prf = a.prf or "sha256"
     if a.tls12:
         return main_tls12(a)
     from tools import rowlib

@@ -150,6 +150,49 @@ class CRecord(ctypes.Structure):
                 ("cid_len", ctypes.c_ubyte), ("cid", ctypes.c_ubyte * 32)]
 
 
+_I32, _U32 = ctypes.c_int32, ctypes.c_uint32
+
+
+class GcmKnobs(ctypes.Structure):
+    """tlsrec::GcmKnobs (csrc/tlsrec_plan.h): the TLSREC_GCM_* / TLSREC_GROUPED switches"""
+    _fields_ = [("waves", _I32), ("wp", _I32), ("g5", _U32), ("treemul", _I32), ("hbuild", _U32), ("pair", _I32),
+                ("grouped", _U32), ("srecs", _U32), ("pair_l", _I32), ("pair_small_min", _U32),
+                ("pair_small_max", _U32), ("pair_big_max", _U32), ("lanes", _U32)]
+
+
+class GcmPlanIn(ctypes.Structure):
+    """tlsrec::GcmPlanIn: what the AES-GCM launch shape is decided from"""
+    _fields_ = [(f, _U32) for f in ("n", "nloaded", "cu", "avg_bytes", "lanes", "nr", "has_cid", "coalesced",
+                                    "keyrun")]
+
+
+class GcmPlan(ctypes.Structure):
+    """tlsrec::GcmPlan: lanes per record, waves, the launch log's waves code, GcmArgs rpw / tm / g5, grid"""
+    _fields_ = [("L", _I32), ("waves", _I32), ("code", _I32), ("rpw", _U32), ("tm", _U32), ("g5", _U32),
+                ("grid", _U32)]
+
+
+class ChachaPlan(ctypes.Structure):
+    _fields_ = [("L", _I32), ("rpw", _U32), ("grid", _U32)]
+
+
+def gcm_plan(knobs=None, **inputs):
+    """tlsrec__gcm_plan over GcmPlanIn(**inputs); knobs None = the process environment's switches"""
+    f = load().tlsrec__gcm_plan
+    f.restype, f.argtypes = None, [ctypes.c_void_p] * 3
+    out = GcmPlan()
+    f(ctypes.byref(GcmPlanIn(**inputs)), ctypes.byref(knobs) if knobs is not None else None, ctypes.byref(out))
+    return out
+
+
+def chacha_plan(n, cu, lanes_in, has_cid):
+    f = load().tlsrec__chacha_plan
+    f.restype, f.argtypes = None, [_U32, _U32, _U32, ctypes.c_int, ctypes.c_void_p]
+    out = ChachaPlan()
+    f(n, cu, lanes_in, has_cid, ctypes.byref(out))
+    return out
+
+
 # every function include/tlsrec.h declares, with its signature
 _VP, _U32, _INT, _SZ = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
 SIGNATURES = {

@@ -19,6 +19,7 @@
 #include "tlsrec_cbc.h"
 #include "tlsrec_frame.h"
 #include "tlsrec_internal.h"
+#include "tlsrec_plan.h"
 
 using namespace tlsrec;
 
@@ -357,185 +358,21 @@ extern "C" int tlsrec__keytab_commit_staged_cbc(tlsrec_keytab *kt, uint32_t firs
     return r;
 }
 
-/* waves per GCM workgroup: 16 (default) or 8; TLSREC_GCM_WAVES overrides */
-static int gcm_waves(void)
+/* The launch shapes are decided in tlsrec_plan.h, host functions without a
+ * device; exported (the release library too) so that they can be checked on a
+ * CPU.  knobs == NULL: the TLSREC_GCM_* switches of the environment. */
+static_assert(PLAN_GCM_WAVES == GCM_WAVES && PLAN_CP_WAVES == CP_WAVES, "tlsrec_plan.h workgroup shapes");
+
+extern "C" uint32_t tlsrec__gcm_pair_small_l(uint32_t rpk) { return gcm_pair_small_l(rpk); }
+
+extern "C" void tlsrec__gcm_plan(const GcmPlanIn *in, const GcmKnobs *knobs, GcmPlan *out)
 {
-    static int w = 0;
-    if (w == 0) {
-        const char *e = getenv("TLSREC_GCM_WAVES");
-        w = (e && atoi(e) == 8) ? 8 : GCM_WAVES;
-    }
-    return w;
+    *out = gcm_plan(*in, knobs ? *knobs : gcm_knobs_from_env());
 }
 
-/* wave-pass GCM variant (per-wave key passes, H^L per wave in LDS) for
- * tables of many keys with very few records each (auto: < 12 per key, where
- * a workgroup-wide key pass leaves most waves idle).  Lanes per record in
- * it: 16 (a wave's 4 records share one key pass) from 3 records per key,
- * 64 below.  Measured, 256 K x 16 KiB AES-256-GCM decrypt (GiB/s):
- *   records/key        1     2     4     8    16    32
- *   wave passes L=16   90   177   415   423   429   433
- *   wave passes L=64  212   228   244   255   259   267
- *   workgroup passes   56   108   208   369   536   584
- * TLSREC_GCM_WP=1 forces it, =0 disables it. */
-static int gcm_wp_env(void)
+extern "C" void tlsrec__chacha_plan(uint32_t n, uint32_t cu, uint32_t lanes_in, int has_cid, ChachaPlan *out)
 {
-    const char *e = getenv("TLSREC_GCM_WP");   /* read per batch: tests switch it */
-    return e ? atoi(e) : -1;
-}
-
-/* 8-lane GCM kernel with the 5-bit GHASH Horner table (gmul5: 104 instead of
- * 128 LDS cycles per multiply); TLSREC_GCM_G5=0 selects the 4-bit table
- * (read per batch: tests and A/B runs switch it) */
-static uint32_t gcm_g5(void)
-{
-    const char *e = getenv("TLSREC_GCM_G5");
-    return (e && atoi(e) == 0) ? 0u : 1u;
-}
-
-/* 16-lane wave passes: the lane tree by table-free multiplies (tlsrec_clmul.h)
- * instead of the key's H^8 / H^4 / H^2 / H^1 tables from HBM (24 KiB more per
- * key pass).  Same-box: k4 455 -> 461 GiB/s, stream 4 x 16 KiB per key
- * receive 424/429 -> 432/432.  TLSREC_GCM_TREEMUL=0 selects the tables. */
-static uint32_t gcm_tm(bool pair, bool wp)
-{
-    /* bit 0: 16-lane wave passes (default on); bit 1: 2- and 4-lane ones
-     * (default on for the paired passes: c4s 740 -> 750 GiB/s same-box; ±1 %
-     * in the 8-wave passes); bit 2: the AAD fold and the two final multiplies
-     * by H as a value too (default on for the paired passes, same-box: c4s
-     * 720 -> 742, k4 549 -> 558, 64 K keys x 16 x 1.4 KiB 362 -> 377 GiB/s:
-     * the key's 8 KiB H^1 table in global memory cost 32 lines per multiply);
-     * bit 3 (r04): lane powers -- AAD and the length block in the lane
-     * layout, one multiply by H^(d+1) per lane and a lane XOR replace the
-     * fold, the tree and the final multiplies (the key-pass kernels then
-     * stage only the Horner table).  Default on for the wave passes, whose
-     * tails were table-free multiplies (same box: k4 582 -> 636 GiB/s, DTLS
-     * 16 x 1.4 KiB +17 %); compiled into the wave-pass kernels only (the
-     * 16-wave key passes' LDS-table tree is cheaper than a VALU multiply on an
-     * LDS-bound kernel, and the run-time flag alone cost c2 5 %, tlsrec_gcm.h). */
-    const char *e = getenv("TLSREC_GCM_TREEMUL");
-    uint32_t tm = e ? (uint32_t) atoi(e) & 15u : (pair ? 15u : (wp ? 9u : 1u));
-    /* bit 4 (r05): the paired passes build the key's Horner table in LDS
-     * from H^L (tlsrec_clmul.h tlsrec_gtab4_window) instead of staging its
-     * 8 KiB from HBM per key pass; TLSREC_GCM_HBUILD=0 stages it */
-    const char *hb = getenv("TLSREC_GCM_HBUILD");
-    if (pair && !(hb && atoi(hb) == 0)) tm |= 16u;
-    return tm;
-}
-
-/* paired wave passes (16 waves, two per key table) for small records of many
- * keys; TLSREC_GCM_PAIR=0 keeps the 8-wave wave passes (read per batch) */
-static int gcm_pair_env(void)
-{
-    const char *e = getenv("TLSREC_GCM_PAIR");
-    return e ? atoi(e) : 1;
-}
-
-/* TLSREC_GROUPED=0: the stream / DTLS layers' batches go through the
- * bucket pass as in r05 (BatchOpt::grouped; A/B and the tests' second path) */
-static bool grouped_env(void)
-{
-    const char *e = getenv("TLSREC_GROUPED");
-    return !(e && atoi(e) == 0);
-}
-
-/* key-ordered descriptor copy for the GCM kernels (bucket scatter):
- * TLSREC_GCM_SRECS=1.  Off by default: same box, k4 665 vs 665-666, c4s 836
- * vs 840-843, c4 1032 vs 1035 GiB/s (profiles/r04h) -- the scattered 40-byte
- * writes cost what the contiguous reads save. */
-static bool srecs_env(void)
-{
-    const char *e = getenv("TLSREC_GCM_SRECS");
-    return e && atoi(e) == 1;
-}
-
-/* lanes per record of the paired passes over small records (2, 4 or 8):
- * measurement override of the records-per-key rule */
-static int gcm_pair_l_env(void)
-{
-    const char *e = getenv("TLSREC_GCM_PAIR_L");
-    const int v = e ? atoi(e) : 0;
-    return (v == 2 || v == 4 || v == 8) ? v : 0;
-}
-
-/* Small records (<= 4 KiB) of many keys take the paired passes from 12 to
- * this many records per key, the 16-wave key passes from there
- * (TLSREC_GCM_PAIR_SMALL_MAX overrides; r04: 128). */
-static uint32_t gcm_pair_small_max(void)
-{
-    const char *e = getenv("TLSREC_GCM_PAIR_SMALL_MAX");
-    return e ? (uint32_t) atoi(e) : 256u;
-}
-
-/* ... and from this many (TLSREC_GCM_PAIR_SMALL_MIN overrides; r04: 12) */
-static uint32_t gcm_pair_small_min(void)
-{
-    const char *e = getenv("TLSREC_GCM_PAIR_SMALL_MIN");
-    return e ? (uint32_t) atoi(e) : 12u;
-}
-
-/* Lanes per record of the paired passes over small records, from the mean
- * records per key (r05).  Each half of a pair takes about rpk / 2 of a key's
- * records in rounds of R = 64 / L records, so a key pass fills
- *     eff(L) = (rpk / 2) / (R * ceil(rpk / (2 R)))
- * of its rounds; the L with the best eff(L) x base(L) wins, base = the
- * full-round rates measured at 64 / 128 records per key (1 400-B AES-256-GCM,
- * 2 : 4 : 8 lanes = 603 : 590 : 530 GiB/s).  The model against the same-box
- * sweep (profiles/r05/small_rpk/), best measured lane count in brackets:
- *   rpk      16  23  32  47  64  95  128  191
- *   model     8   4   4   8   2   4    2    2
- *   [best]    8   4   4   8   2   4    2    2
- * r04's rule (2 from 48, 4 from 24, else 8) lost 14-29 % at 47 and 95 per
- * key, and the 16-wave key passes it used from 128 per key 13-25 %. */
-extern "C" uint32_t tlsrec__gcm_pair_small_l(uint32_t rpk)
-{
-    static const uint32_t Ls[3] = { 2, 4, 8 };
-    static const double base[3] = { 1.0, 590.0 / 603.0, 530.0 / 603.0 };
-    double best = -1.0;
-    uint32_t bl = 8;
-    const double h = rpk / 2.0;
-    for (int i = 0; i < 3; i++) {
-        const double R = 64.0 / Ls[i];
-        const double rounds = ceil(h / R);
-        const double score = rounds > 0 ? base[i] * h / (R * rounds) : 0.0;
-        if (score > best + 1e-9) {
-            best = score;
-            bl = Ls[i];
-        }
-    }
-    return bl;
-}
-
-/* Large records (> 4 KiB) take the paired passes below this many records per
- * key (r05: 40; r04: 12).  With the rounds starting at each key's first
- * position (tlsrec_gcm.h), 16 KiB records, 2^18 records (same box,
- * profiles/r05/pair_big), 16-wave key passes -> paired 16 lanes:
- *   records per key     16          23          32          47
- *   GiB/s            637 -> 705  638 -> 667  667 -> 711  668 -> 654
- * and the stream layer's 64 K connections x 16 x 16 KiB receive / send
- * 602 -> 685 / 497 -> 542.  At 64 per key one key fills a key pass's 16
- * waves exactly and the key passes stay (c4).  TLSREC_GCM_PAIR_BIG_MAX
- * overrides. */
-static uint32_t gcm_pair_big_max(void)
-{
-    const char *e = getenv("TLSREC_GCM_PAIR_BIG_MAX");
-    return e ? (uint32_t) atoi(e) : 40u;
-}
-
-/* lanes per GCM record when the caller passes 0 (auto): measurement override */
-static uint32_t gcm_lanes_env(void)
-{
-    const char *e = getenv("TLSREC_GCM_LANES");
-    return e ? (uint32_t) atoi(e) : 0u;
-}
-
-static uint32_t pick_rpw(uint64_t n, uint32_t waves_per_wg, uint32_t R, uint32_t target_wgs)
-{
-    uint64_t want = (n + (uint64_t) waves_per_wg * target_wgs - 1) / ((uint64_t) waves_per_wg * target_wgs);
-    if (want < R) want = R;
-    want = (want + R - 1) / R * R;
-    if (want > 64) want = 64;
-    return (uint32_t) want;
+    *out = chacha_plan(n, cu, lanes_in, has_cid != 0);
 }
 
 /* ---- per-stream device scratch (tlsrec_internal.h) ---- */
@@ -701,14 +538,34 @@ struct BucketScratch {
     size_t scan_bytes;
 };
 
+/* The bucket pass's classes, in the order of its keys (BucketArgs): a class of
+ * `capacity` keys per slot kind, except ChaCha20-Poly1305's CP_SPREAD counters. */
+enum BucketClass {
+    BC_AES_GCM = 0,       /* + 0 / 1 / 2: AES-128 / -256 / -192-GCM */
+    BC_CCM = 3,
+    BC_CHACHA = 4,
+    BC_ALT_GCM = 5,       /* + 0 .. 5: ARIA-128/192/256-GCM, Camellia-128/192/256-GCM */
+    BC_CBC = 11,          /* counted only while the table holds a CBC slot */
+    BC_IDENTITY = -1      /* no class: the descriptors in their own order, whatever the batch's */
+};
+
+struct ClassRange {
+    size_t lo, hi;        /* the class's keys [lo, hi): where its offsets start in BucketScratch::offs */
+};
+
+static ClassRange bucket_class_range(int cls, uint32_t capacity)
+{
+    const size_t cap = capacity;
+    if (cls < BC_CHACHA) return { cls * cap, (cls + 1) * cap };
+    if (cls == BC_CHACHA) return { 4 * cap, 4 * cap + CP_SPREAD };
+    return { (cls - 1) * cap + CP_SPREAD, cls * cap + CP_SPREAD };
+}
+
 static int bucket(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res, uint32_t n,
                   hipStream_t st, BucketScratch &b)
 {
-    /* AES-128-GCM, AES-256-GCM, AES-192-GCM, AES-CCM slots, ChaCha, ARIA-128/192/256-GCM,
-     * Camellia-128/192/256-GCM slots, end */
-    /* ... and, only while the table holds one, the AES-CBC class */
-    const uint32_t cbc_mask = (1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC);
-    const size_t nk = ((kt->cipher_mask & cbc_mask) ? 11 : 10) * (size_t) kt->capacity + CP_SPREAD + 1;
+    /* every class up to the last the table can hold, and the end */
+    const size_t nk = bucket_class_range((kt->cipher_mask & CBC_CIPHER_BITS) ? BC_CBC : BC_CBC - 1, kt->capacity).hi + 1;
     b.scan_bytes = tlsrec__scan_scratch_bytes((uint32_t) nk);
     const size_t al = 256;
     const size_t szk = (nk * 4 + al - 1) / al * al, szp = ((size_t) n * 4 + al - 1) / al * al;
@@ -746,11 +603,6 @@ static int bucket(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_
     return 0;
 }
 
-/* only_cipher: launch only that cipher's kernel (the single-record engine,
- * which knows the record's slot on the host); 0 = every cipher loaded. */
-/* avg_bytes: mean record size when the caller knows it (the stream / DTLS
- * layers and the host pipeline do; 0 = unknown) -- it decides the GCM launch
- * for many keys with little work each (below). */
 /* Test hooks (tlsrec_internal.h TLSREC_HOOK_SKIP; the test build only, as the
  * reference compiles its own under MBEDTLS_TEST_HOOKS, ssl_misc.h:2685):
  *   tlsrec__test_skip_record   the AEAD kernels leave this record index
@@ -844,320 +696,221 @@ struct BatchOpt {
                                             never loaded (no CBC kernel; its records get the bad-slot result) */
 };
 
+/* Batch work takes the CUs the record server holds (server.hip): yield first,
+ * note the batch's stream on every way out (the server launches no grid
+ * between the two). */
+struct YieldGuard {
+    hipStream_t st;
+    bool on;
+    int counted;      /* the yield counted this batch as queueing (only then does the note uncount it) */
+    YieldGuard(hipStream_t s, bool o) : st(s), on(o), counted(o ? tlsrec__server_yield() : 0) {}
+    ~YieldGuard() { if (on) tlsrec__server_note_batch(st, counted); }
+};
+
+/* What every launch of one batch is given. */
+struct BatchView {
+    const tlsrec_keytab *kt;
+    const tlsrec_batch_rec *recs;
+    tlsrec_batch_res *res;
+    uint32_t n;
+    const uint8_t *in;
+    uint8_t *out;
+    hipStream_t st;
+    int dec;
+    uint32_t cmask;             /* 1 << TLSREC_CIPHER_* of the kernels to launch */
+    uint32_t skip;              /* test hook (tlsrec__test_skip_record) */
+    const BucketScratch *bs;    /* the bucket pass's order; nullptr = identity order */
+};
+
+static const uint32_t GCM_CIPHER_BITS =
+    (1u << TLSREC_CIPHER_AES_128_GCM) | (1u << TLSREC_CIPHER_AES_256_GCM) | (1u << TLSREC_CIPHER_AES_192_GCM) |
+    (1u << TLSREC_CIPHER_ARIA_128_GCM) | (1u << TLSREC_CIPHER_ARIA_192_GCM) | (1u << TLSREC_CIPHER_ARIA_256_GCM) |
+    (1u << TLSREC_CIPHER_CAMELLIA_128_GCM) | (1u << TLSREC_CIPHER_CAMELLIA_192_GCM) |
+    (1u << TLSREC_CIPHER_CAMELLIA_256_GCM);
+
+/* The fields GcmArgs, CpArgs, CcmArgs and CbcArgs share, for the records of
+ * bucket class cls; every other field zero or its default. */
+template <class A> static A class_args(const BatchView &v, int cls)
+{
+    A a = A();
+    a.slots = v.kt->d_slots;
+    a.recs = v.recs;
+    a.res = v.res;
+    a.n = v.n;
+    if (v.bs && cls != BC_IDENTITY) {
+        const ClassRange r = bucket_class_range(cls, v.kt->capacity);
+        a.perm = v.bs->perm;
+        a.lo = v.bs->offs + r.lo;
+        a.hi = v.bs->offs + r.hi;
+    }
+    a.in = v.in;
+    a.out = v.out;
+    a.capacity = v.kt->capacity;
+    a.skip = v.skip;
+    return a;
+}
+
+static GcmArgs gcm_args(const BatchView &v, int cls, int cipher)
+{
+    GcmArgs a = class_args<GcmArgs>(v, cls);
+    a.ghtab = v.kt->d_ghtab;
+    a.dummy = v.kt->d_dummy;
+    a.srecs = v.bs ? v.bs->srecs : nullptr;
+    a.cipher = (uint32_t) cipher;
+    return a;
+}
+
+/* A table holding a single key, or a batch of one record, needs no grouping:
+ * the kernels walk the descriptors in order and flag records naming an
+ * unusable slot.  Neither does (r05) a table of ChaCha20-Poly1305 keys only:
+ * its kernel walks records in arrival order, with or without the bucket
+ * pass's permutation (the count / scan / scatter kernels cost 5-6 % of a
+ * 1 M-record stream or DTLS batch), nor do (r06) records already grouped by
+ * key -- the stream and DTLS layers emit each connection's records together,
+ * and the GCM passes find a key's run of records where they lie (~90 us of a
+ * 1 M-record call).  Otherwise the bucket pass groups the records by key.
+ * Either way every result reads INTERNAL_ERROR before the AEAD kernels run
+ * (the guard kernel, or the bucket count kernel), so a record that no kernel
+ * reaches fails closed -- the reference's auth_done check, ssl_msg.c:1260 /
+ * :1804. */
+static int order_records(BatchView &v, const BatchOpt &opt, const GcmKnobs &knobs, bool identity, BucketScratch &bs)
+{
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_BUCKET, !identity, 0, 0, 0);
+    if (identity)
+        return opt.prefilled ? 0 : hip_ok(tlsrec__launch_res_guard(v.res, v.n, v.st));
+    bs.want_srecs = (v.cmask & GCM_CIPHER_BITS) != 0 && knobs.srecs;
+    const int r = bucket(v.kt, v.recs, v.res, v.n, v.st, bs);
+    if (!r) v.bs = &bs;
+    return r;
+}
+
+/* AES-GCM: one launch per key size the table holds, shaped by gcm_plan() */
+static int launch_aes_gcm(const BatchView &v, const BatchOpt &opt, const GcmKnobs &knobs, uint32_t lanes, bool keyrun)
+{
+    static const int ciphers[3] = { TLSREC_CIPHER_AES_128_GCM, TLSREC_CIPHER_AES_256_GCM, TLSREC_CIPHER_AES_192_GCM };
+    GcmPlanIn in;
+    in.n = v.n;
+    in.nloaded = v.kt->nloaded;     /* read once: the engine's pages change under it */
+    in.cu = (uint32_t) v.kt->cu;
+    in.avg_bytes = opt.avg_bytes;
+    in.lanes = lanes ? lanes : knobs.lanes;
+    in.has_cid = v.kt->has_cid;
+    in.coalesced = opt.coalesced;
+    in.keyrun = keyrun;
+    for (int ci = 0; ci < 3; ci++) {
+        if (!(v.cmask & (1u << ciphers[ci]))) continue;
+        in.nr = tlsrec_cipher_nr(ciphers[ci]);
+        const GcmPlan p = gcm_plan(in, knobs);
+        GcmArgs a = gcm_args(v, BC_AES_GCM + ci, ciphers[ci]);
+        a.rpw = p.rpw;
+        a.g5 = p.g5;
+        a.tm = p.tm;
+        a.src_off = v.dec ? nullptr : opt.src_off;
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_GCM, p.L, p.code, a.tm, a.src_off != nullptr);
+        if (tlsrec__launch_gcm(&a, v.dec, p.L, (int) in.nr, p.code, p.grid, v.st) != hipSuccess)
+            return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
+    return 0;
+}
+
+/* ARIA-GCM and Camellia-GCM: the GCM kernel around the LDS-table cipher, one
+ * configuration (8 lanes, 16 waves) */
+static int launch_alt_gcm(const BatchView &v)
+{
+    static const int ciphers[6] = { TLSREC_CIPHER_ARIA_128_GCM, TLSREC_CIPHER_ARIA_192_GCM,
+                                    TLSREC_CIPHER_ARIA_256_GCM, TLSREC_CIPHER_CAMELLIA_128_GCM,
+                                    TLSREC_CIPHER_CAMELLIA_192_GCM, TLSREC_CIPHER_CAMELLIA_256_GCM };
+    for (int ci = 0; ci < 6; ci++) {
+        const int c = ciphers[ci];
+        if (!(v.cmask & (1u << c))) continue;
+        GcmArgs a = gcm_args(v, BC_ALT_GCM + ci, c);
+        a.rpw = pick_rpw(v.n, (uint32_t) ARIA_GCM_WAVES, 8u, (uint32_t) v.kt->cu);
+        const uint32_t grid = plan_grid(v.n, (uint32_t) ARIA_GCM_WAVES, a.rpw);
+        TLSREC_LAUNCH_LOG(TLSREC_LOG_ALT_GCM, c, 0, 0, 0);
+        if (tlsrec__launch_gcm_aria(&a, v.dec, (int) tlsrec_cipher_alt_nr(c), (int) v.kt->has_cid, grid, v.st) !=
+            hipSuccess)
+            return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
+    return 0;
+}
+
+/* CCM, every block cipher: one launch, the rounds the table holds as a mask */
+static int launch_ccm(const BatchView &v)
+{
+    uint32_t ccm_nr = 0;
+    for (int c = TLSREC_CIPHER_AES_128_CCM; c <= TLSREC_CIPHER_AES_256_CCM_8; c++)
+        if (v.cmask & (1u << c)) ccm_nr |= 1u << tlsrec_cipher_nr(c);
+    for (int c = TLSREC_CIPHER_ARIA_128_CCM; c <= TLSREC_CIPHER_CAMELLIA_256_CCM; c++)   /* ARIA / Camellia: bit nr + 4 */
+        if (tlsrec_cipher_is_alt_ccm(c) && (v.cmask & (1u << c))) ccm_nr |= 1u << (tlsrec_cipher_alt_nr(c) + 4);
+    if (!ccm_nr) return 0;
+    CcmArgs a = class_args<CcmArgs>(v, BC_CCM);
+    a.cid = v.kt->has_cid;
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_CCM, ccm_nr, 0, 0, 0);
+    return hip_ok(tlsrec__launch_ccm(&a, v.dec, ccm_nr, v.st));
+}
+
+/* AES-CBC + HMAC: one launch per (key size, MAC) the table holds */
+static int launch_cbc(const BatchView &v)
+{
+    if (!(v.cmask & CBC_CIPHER_BITS)) return 0;
+    uint32_t variants = v.kt->cbc_variants;
+    if (!(v.cmask & (1u << TLSREC_CIPHER_AES_128_CBC))) variants &= ~7u;
+    if (!(v.cmask & (1u << TLSREC_CIPHER_AES_256_CBC))) variants &= 7u;
+    CbcArgs a = class_args<CbcArgs>(v, BC_CBC);
+    a.ghtab = v.kt->d_ghtab;
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC, v.dec, ((variants | (variants >> 3)) & 7u) << 1, v.kt->cbc_etm, 0);
+    return hip_ok(tlsrec__launch_cbc(&a, v.dec, variants, v.st));
+}
+
+/* ChaCha20-Poly1305, shaped by chacha_plan(); lanes_in: the caller's own request */
+static int launch_chacha(const BatchView &v, const BatchOpt &opt, uint32_t lanes_in)
+{
+    if (!(v.cmask & (1u << TLSREC_CIPHER_CHACHA20_POLY1305))) return 0;
+    const ChachaPlan p = chacha_plan(v.n, (uint32_t) v.kt->cu, lanes_in, v.kt->has_cid != 0);
+    CpArgs a = class_args<CpArgs>(v, BC_CHACHA);
+    a.rpw = p.rpw;
+    a.cid = v.kt->has_cid;
+    a.src_off = v.dec ? nullptr : opt.src_off;
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_CHACHA, p.L, a.src_off != nullptr, 0, 0);
+    return hip_ok(tlsrec__launch_chachapoly(&a, v.dec, p.L, p.grid, v.st));
+}
+
+/* BatchOpt::no_cbc over a table with CBC slots: their records get the bad-slot result */
+static int launch_cbc_refusal(const BatchView &v, const BatchOpt &opt)
+{
+    if (!opt.no_cbc || !(v.kt->cipher_mask & CBC_CIPHER_BITS)) return 0;
+    CbcArgs a = class_args<CbcArgs>(v, BC_IDENTITY);
+    a.ghtab = v.kt->d_ghtab;
+    return hip_ok(tlsrec__launch_cbc_refuse(&a, v.st));
+}
+
 static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res, uint32_t n,
                  const uint8_t *in, uint8_t *out, uint32_t lanes, void *stream, int dec, const BatchOpt &opt = BatchOpt())
 {
     if (!kt || (!recs && n) || (!res && n)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
-    const int cu = kt->cu;
-    const uint32_t avg_bytes = opt.avg_bytes;
-    const bool prefilled = opt.prefilled;
+    YieldGuard yg(st, !opt.coalesced);
+    const GcmKnobs knobs = gcm_knobs_from_env();
     const uint32_t cmask = (opt.only_mask ? (kt->cipher_mask & opt.only_mask) : kt->cipher_mask) &
                            (opt.no_cbc ? ~CBC_CIPHER_BITS : ~0u);
-    const uint32_t skip = g_test_skip;
-    /* A table holding a single key, or a batch of one record, needs no
-     * grouping: the kernels walk the descriptors in order and flag records
-     * naming an unusable slot.  Otherwise the bucket pass groups GCM records
-     * by key (then ChaCha).  Either way every result reads INTERNAL_ERROR
-     * before the AEAD kernels run (the guard kernel, or the bucket count
-     * kernel), so a record that no kernel reaches fails closed -- the
-     * reference's auth_done check, ssl_msg.c:1260 / :1804. */
-    /* batch work takes the CUs the record server holds (server.hip): yield
-     * now, note the batch's stream on every way out (the server launches no
-     * grid between the two) */
-    struct YieldGuard {
-        hipStream_t st;
-        bool on;
-        int counted;      /* the yield counted this batch as queueing (only then does the note uncount it) */
-        ~YieldGuard() { if (on) tlsrec__server_note_batch(st, counted); }
-    } yg{ st, !opt.coalesced, 0 };
-    if (yg.on) yg.counted = tlsrec__server_yield();
-    BucketScratch bs;
-    /* (r05) a table of ChaCha20-Poly1305 keys only needs no grouping either:
-     * its kernel walks records in arrival order, with or without the bucket
-     * pass's permutation, and flags unusable slots in identity order -- the
-     * count / scan / scatter kernels cost 5-6 % of a 1 M-record stream or
-     * DTLS batch */
-    /* (r06) records already grouped by key -- the stream and DTLS layers emit
-     * each connection's records together -- need no bucket pass either: the
-     * GCM passes find a key's run of records where they lie (the bucket
-     * count / scan / scatter kernels were ~90 us of a 1 M-record call);
-     * TLSREC_GROUPED=0 sends them through the bucket pass as before */
-    const bool grouped = opt.grouped && grouped_env();
+    BatchView v = { kt, recs, res, n, in, out, st, dec, cmask, g_test_skip, nullptr };
+    const bool grouped = opt.grouped && knobs.grouped;
     const bool identity = kt->nloaded == 1 || n == 1 || opt.coalesced || grouped ||
                           kt->cipher_mask == (1u << TLSREC_CIPHER_CHACHA20_POLY1305);
     const bool keyrun = !identity || grouped;     /* the many-keys launch shapes apply */
-    TLSREC_LAUNCH_LOG(TLSREC_LOG_BUCKET, !identity, 0, 0, 0);
-    if (identity) {
-        if (!prefilled && tlsrec__launch_res_guard(res, n, st) != hipSuccess) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    } else {
-        const uint32_t gcm_mask = (1u << TLSREC_CIPHER_AES_128_GCM) | (1u << TLSREC_CIPHER_AES_256_GCM) |
-                                  (1u << TLSREC_CIPHER_AES_192_GCM) | (1u << TLSREC_CIPHER_ARIA_128_GCM) |
-                                  (1u << TLSREC_CIPHER_ARIA_192_GCM) | (1u << TLSREC_CIPHER_ARIA_256_GCM) |
-                                  (1u << TLSREC_CIPHER_CAMELLIA_128_GCM) | (1u << TLSREC_CIPHER_CAMELLIA_192_GCM) |
-                                  (1u << TLSREC_CIPHER_CAMELLIA_256_GCM);
-        bs.want_srecs = (cmask & gcm_mask) != 0 && srecs_env();
-        int r = bucket(kt, recs, res, n, st, bs);
-        if (r) {
-            tlsrec__scratch_release(&bs.lease);
-            return r;
-        }
-    }
-    const uint32_t cap = kt->capacity;
-    int rc = 0;
-    static const int gcm_ciphers[3] = { TLSREC_CIPHER_AES_128_GCM, TLSREC_CIPHER_AES_256_GCM,
-                                        TLSREC_CIPHER_AES_192_GCM };
-    const uint32_t lanes_in = lanes;
-    if (!lanes) lanes = gcm_lanes_env();
-    for (int ci = 0; ci < 3 && !rc; ci++) {
-        const int cipher = gcm_ciphers[ci];     /* bucket class ci: keys [ci * cap, (ci + 1) * cap) */
-        if (!(cmask & (1u << cipher))) continue;
-        /* (ARIA-GCM below: one configuration) */
-        /* lanes per record: a key pass should still fill the 16 waves of a
-         * workgroup.  8 for a single key or >= 128 records per key; 16
-         * (4 records per wave) down to 48 records per key; 64 (one record per
-         * wave) below that -- the many-connections, few-records regime of
-         * the stream path. */
-        const uint32_t nl = kt->nloaded;     /* read once: the engine's pages change under it */
-        const uint32_t rpk = nl > 1 ? n / nl : n;
-        /* ... and the batch should fill the chip: with fewer than 8 records
-         * per wave of a full grid (cu x 16 waves), more lanes per record
-         * (measured at 16 K x 16 KiB records: L = 8 363, L = 16 611, L = 64
-         * 536 GiB/s) */
-        const uint64_t rpwave = (uint64_t) n / ((uint64_t) cu * GCM_WAVES);
-        const int Lfill = rpwave >= 8 ? 8 : (rpwave >= 2 ? 16 : 64);
-        int L = (lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 64) ? (int) lanes
-                : (nl <= 1 || rpk >= 128) ? 8 : (rpk >= 48 ? 16 : 64);
-        if (!(lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 64) && Lfill > L) L = Lfill;
-        /* one key, small records (<= 4 KiB, size hint): 4 lanes per record
-         * (16 records per wave round) once the batch fills the chip at that --
-         * half the lane tree and twice the records in flight per wave.  Same
-         * box (r04r): c2s 592/582 -> 652/661, c2se 610/604 -> 682/681 GiB/s;
-         * 16 KiB records keep 8 (c2 750/742 at 8, 732/737 at 4). */
-        if (!(lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 64) && nl <= 1 && L == 8 &&
-            rpwave >= 16 && avg_bytes != 0 && avg_bytes <= 4096)
-            L = 4;
-        if (kt->has_cid) L = 8;     /* the CID variant: one configuration */
-        GcmArgs a;
-        a.slots = kt->d_slots;
-        a.ghtab = kt->d_ghtab;
-        a.dummy = kt->d_dummy;
-        a.recs = recs;
-        a.res = res;
-        a.n = n;
-        a.perm = identity ? nullptr : bs.perm;
-        a.srecs = identity ? nullptr : bs.srecs;
-        a.lo = identity ? nullptr : bs.offs + (size_t) ci * cap;
-        a.hi = identity ? nullptr : bs.offs + (size_t) (ci + 1) * cap;
-        a.in = in;
-        a.out = out;
-        int nr = (int) tlsrec_cipher_nr(cipher);
-        const int wpe = gcm_wp_env();
-        const bool auto_l = !(lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 64);
-        /* wave passes (each wave stages only its key's H^L table, no
-         * workgroup barriers) for few records per key, or -- when the record
-         * size is known -- for keys with under 64 KiB of records each (same-box
-         * measurements: 16 x 1.4 KiB per key 198 -> 313 GiB/s, DTLS 125 -> 231;
-         * 16 x 16 KiB and 64 x 1.4 KiB per key stay faster with key passes) */
-        /* 4 lanes (16 records of the key per wave round) when the keys'
-         * records are small, 12..127 each, and the batch fills the chip at 16
-         * records per wave: one GHASH lane tree per 16 records instead of per
-         * 4, and only the tree tables H^1, H^2 read from HBM.  Same-box, 1.4 KiB
-         * records (L = 16 wave passes or L = 16 key passes before):
-         *   64 K keys x 16, DTLS AES-128-GCM   receive 232 -> 390, send 212 -> 328 GiB/s
-         *   64 K keys x 16, stream AES-256-GCM receive 198 -> 335, send 200 -> 294
-         *   16 K keys x 64, stream AES-256-GCM receive 317 -> 357, send 282 -> 324
-         *   c4s (64 K keys x 64, GCM + ChaCha)  486 -> 541
-         * and 2 lanes (32 records per round, the tree only H^1) from 48 records
-         * per key: 16 K keys x 64 stream receive 353 -> 375, send 319 -> 332,
-         * c4s 536 -> 549 (at 16 per key 2 lanes idle half the wave: 388 -> 254). */
-        const bool small = avg_bytes != 0 && avg_bytes <= 4096 && rpk >= 12 && rpk < 128;
-        const bool small2 = small && rpk >= 48 && (uint64_t) n >= (uint64_t) cu * 8 * 32;
-        const bool small4 = small && !small2 && (uint64_t) n >= (uint64_t) cu * 8 * 16;
-        const bool light = rpk < 12 || (avg_bytes != 0 && rpk < 48 && (uint64_t) rpk * avg_bytes < 65536u) ||
-                           small2 || small4;
-        if (auto_l && !kt->has_cid && keyrun && nr != 12 && wpe != 0 && light)
-            L = small2 ? 2 : (small4 ? 4 : ((rpk >= 3 && Lfill <= 16) ? 16 : 64));
-        bool wp = !kt->has_cid && keyrun && (L == 2 || L == 4 || L == 16 || L == 64) && nr != 12 &&
-                  (wpe == 1 || (wpe != 0 && light));
-        if (opt.coalesced && n > 1 && auto_l && !kt->has_cid && nr != 12) {
-            L = 64;        /* a wave per record, 64 lanes on it: each wave its own record's key, in parallel */
-            wp = true;
-        }
-        /* Paired wave passes: small records (<= 4 KiB), 12..127 per key.  The
-         * 8-wave passes above hold one 8 KiB H^L table per wave beside the
-         * 64 KiB T-tables, so they run at half the single-key kernel's
-         * occupancy and wait on LDS latency (r02 PMC, DTLS 16 x 1.4 KiB per
-         * key: LDS 35 %, VALU 53 % busy); with two waves per table, 16 waves
-         * fit.  Each wave takes half of a key's records, so L is picked for
-         * a round to hold that half: 2 lanes (32 records) from 48 records per
-         * key, 4 from 24, 8 below. */
-        /* Large records (known > 4 KiB) with 4..11 per key (k4, 16 KiB
-         * streams): the same pairing at 16 or 32 lanes, 4 or 2 records of a key
-         * per wave. */
-        /* (r05: small records up to 255 per key, L by the round-fill model of
-         * tlsrec__gcm_pair_small_l) */
-        bool pair = false;
-        /* (r06) the paired kernels hold lane powers only (tlsrec_gcm.h): a
-         * coalesced call or a TREEMUL mode without bit 3 takes the 8-wave passes */
-        if (auto_l && !kt->has_cid && keyrun && nr != 12 && wpe != 0 && gcm_pair_env() && avg_bytes != 0 &&
-            !opt.coalesced && (gcm_tm(true, true) & 8u)) {
-            int Lp = 0;
-            const bool small_pair = avg_bytes <= 4096 && rpk >= gcm_pair_small_min() && rpk < gcm_pair_small_max();
-            if (small_pair) Lp = (int) tlsrec__gcm_pair_small_l(rpk);
-            if (small_pair && gcm_pair_l_env()) Lp = gcm_pair_l_env();     /* measurement override */
-            else if (avg_bytes > 4096 && rpk >= 4 && rpk < gcm_pair_big_max()) Lp = rpk >= 8 ? 16 : 32;
-            if (Lp && (uint64_t) n >= (uint64_t) cu * 16 * (uint64_t) (64 / Lp)) {
-                L = Lp;
-                wp = pair = true;
-            }
-        }
-        if (L == 2 && !wp) L = 4;     /* 2 lanes: wave passes only */
-        const int waves = pair ? 16 : (wp ? 8 : (kt->has_cid ? 16 : gcm_waves()));
-        a.rpw = (opt.coalesced && wp) ? 1u : pick_rpw(n, (uint32_t) waves, 64 / L, (uint32_t) cu);
-        a.src_off = dec ? nullptr : opt.src_off;
-        a.capacity = cap;
-        a.cipher = (uint32_t) cipher;
-        a.g5 = gcm_g5();
-        /* coalesced calls wait on the lane tree: from the key's tables (one
-         * L2 round trip per level) rather than table-free (~1 700 dependent
-         * VALU ticks per level) */
-        a.tm = opt.coalesced ? 0u : gcm_tm(pair, wp);
-        a.skip = skip;
-        uint64_t per_wg = (uint64_t) waves * a.rpw;
-        uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_GCM, L, pair ? -32 : (wp ? -8 : (kt->has_cid ? -16 : waves)), a.tm,
-                          a.src_off != nullptr);
-        if (tlsrec__launch_gcm(&a, dec, L, nr, pair ? -32 : (wp ? -8 : (kt->has_cid ? -16 : waves)), grid, st) !=
-            hipSuccess)
-            rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    /* ARIA-GCM and Camellia-GCM: the GCM kernel around the LDS-table cipher
-     * (8 lanes, 16 waves); bucket classes (4, 5, 6) cap + CP_SPREAD and (7, 8, 9) cap + CP_SPREAD */
-    static const int alt_gcm[6] = { TLSREC_CIPHER_ARIA_128_GCM, TLSREC_CIPHER_ARIA_192_GCM, TLSREC_CIPHER_ARIA_256_GCM,
-                                    TLSREC_CIPHER_CAMELLIA_128_GCM, TLSREC_CIPHER_CAMELLIA_192_GCM,
-                                    TLSREC_CIPHER_CAMELLIA_256_GCM };
-    for (int ci = 0; ci < 6 && !rc; ci++) {
-        const int c = alt_gcm[ci];
-        if (!(cmask & (1u << c))) continue;
-        const size_t base = (size_t) (4 + ci) * cap + CP_SPREAD;
-        GcmArgs a;
-        a.slots = kt->d_slots;
-        a.ghtab = kt->d_ghtab;
-        a.dummy = kt->d_dummy;
-        a.recs = recs;
-        a.res = res;
-        a.n = n;
-        a.perm = identity ? nullptr : bs.perm;
-        a.srecs = identity ? nullptr : bs.srecs;
-        a.lo = identity ? nullptr : bs.offs + base;
-        a.hi = identity ? nullptr : bs.offs + base + cap;
-        a.in = in;
-        a.out = out;
-        a.rpw = pick_rpw(n, (uint32_t) ARIA_GCM_WAVES, 8u, (uint32_t) cu);
-        a.src_off = nullptr;
-        a.capacity = cap;
-        a.cipher = (uint32_t) c;
-        a.g5 = 0;
-        a.tm = 0;
-        a.skip = skip;
-        const uint64_t per_wg = (uint64_t) ARIA_GCM_WAVES * a.rpw;
-        const uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_ALT_GCM, c, 0, 0, 0);
-        if (tlsrec__launch_gcm_aria(&a, dec, (int) tlsrec_cipher_alt_nr(c), (int) kt->has_cid, grid, st) != hipSuccess)
-            rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    uint32_t ccm_nr = 0;
-    for (int c = TLSREC_CIPHER_AES_128_CCM; c <= TLSREC_CIPHER_AES_256_CCM_8; c++)
-        if (cmask & (1u << c)) ccm_nr |= 1u << tlsrec_cipher_nr(c);
-    for (int c = TLSREC_CIPHER_ARIA_128_CCM; c <= TLSREC_CIPHER_CAMELLIA_256_CCM; c++)   /* ARIA / Camellia: bit nr + 4 */
-        if (tlsrec_cipher_is_alt_ccm(c) && (cmask & (1u << c))) ccm_nr |= 1u << (tlsrec_cipher_alt_nr(c) + 4);
-    if (!rc && ccm_nr) {
-        CcmArgs a;
-        a.slots = kt->d_slots;
-        a.recs = recs;
-        a.res = res;
-        a.n = n;
-        a.perm = identity ? nullptr : bs.perm;
-        a.lo = identity ? nullptr : bs.offs + 3 * (size_t) cap;
-        a.hi = identity ? nullptr : bs.offs + 4 * (size_t) cap;
-        a.in = in;
-        a.out = out;
-        a.capacity = cap;
-        a.flag_nr = 0;
-        a.cid = kt->has_cid;
-        a.skip = skip;
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_CCM, ccm_nr, 0, 0, 0);
-        if (tlsrec__launch_ccm(&a, dec, ccm_nr, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    /* AES-CBC + HMAC: one launch per (key size, MAC) the table holds, over
-     * bucket class 10 cap + CP_SPREAD */
-    if (!rc && (cmask & ((1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC)))) {
-        uint32_t variants = kt->cbc_variants;
-        if (!(cmask & (1u << TLSREC_CIPHER_AES_128_CBC))) variants &= ~7u;
-        if (!(cmask & (1u << TLSREC_CIPHER_AES_256_CBC))) variants &= 7u;
-        CbcArgs a;
-        a.slots = kt->d_slots;
-        a.ghtab = kt->d_ghtab;
-        a.recs = recs;
-        a.res = res;
-        a.n = n;
-        a.perm = identity ? nullptr : bs.perm;
-        a.lo = identity ? nullptr : bs.offs + 10 * (size_t) cap + CP_SPREAD;
-        a.hi = identity ? nullptr : bs.offs + 11 * (size_t) cap + CP_SPREAD;
-        a.in = in;
-        a.out = out;
-        a.capacity = cap;
-        a.skip = skip;
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC, dec, ((variants | (variants >> 3)) & 7u) << 1, kt->cbc_etm, 0);
-        if (tlsrec__launch_cbc(&a, dec, variants, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    if (!rc && (cmask & (1u << TLSREC_CIPHER_CHACHA20_POLY1305))) {
-        /* 2 lanes per record, more when the batch would not fill the chip
-         * (cu x 8 resident waves: 2 per SIMD) */
-        const uint64_t rpwave = (uint64_t) n / ((uint64_t) cu * 8);
-        int L = (lanes_in == 1 || lanes_in == 2 || lanes_in == 4 || lanes_in == 8) ? (int) lanes_in
-                : (rpwave >= 32 ? 2 : (rpwave >= 16 ? 4 : 8));
-        if (kt->has_cid) L = 2;     /* the CID variant: one configuration */
-        CpArgs a;
-        a.slots = kt->d_slots;
-        a.recs = recs;
-        a.res = res;
-        a.n = n;
-        a.perm = identity ? nullptr : bs.perm;
-        a.lo = identity ? nullptr : bs.offs + 4 * (size_t) cap;
-        a.hi = identity ? nullptr : bs.offs + 4 * (size_t) cap + CP_SPREAD;
-        a.in = in;
-        a.out = out;
-        a.rpw = pick_rpw(n, CP_WAVES, 64 / L, (uint32_t) cu * 4);
-        a.capacity = cap;
-        a.cid = kt->has_cid;
-        a.skip = skip;
-        a.src_off = dec ? nullptr : opt.src_off;
-        uint64_t per_wg = (uint64_t) CP_WAVES * a.rpw;
-        uint32_t grid = (uint32_t) ((n + per_wg - 1) / per_wg);
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_CHACHA, L, a.src_off != nullptr, 0, 0);
-        if (tlsrec__launch_chachapoly(&a, dec, L, grid, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    if (!rc && opt.no_cbc && (kt->cipher_mask & CBC_CIPHER_BITS)) {
-        CbcArgs a;
-        a.slots = kt->d_slots;
-        a.ghtab = kt->d_ghtab;
-        a.recs = recs;
-        a.res = res;
-        a.n = n;
-        a.perm = nullptr;
-        a.lo = a.hi = nullptr;
-        a.in = in;
-        a.out = out;
-        a.capacity = kt->capacity;
-        a.skip = skip;
-        if (tlsrec__launch_cbc_refuse(&a, st) != hipSuccess) rc = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
+    BucketScratch bs;
+    int rc = order_records(v, opt, knobs, identity, bs);
+    if (!rc) rc = launch_aes_gcm(v, opt, knobs, lanes, keyrun);
+    if (!rc) rc = launch_alt_gcm(v);
+    if (!rc) rc = launch_ccm(v);
+    if (!rc) rc = launch_cbc(v);
+    if (!rc) rc = launch_chacha(v, opt, lanes);
+    if (!rc) rc = launch_cbc_refusal(v, opt);
     tlsrec__scratch_release(&bs.lease);
     return rc;
 }
+
 
 extern "C" int tlsrec_batch_encrypt(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res,
                                     uint32_t n, const uint8_t *in_arena, uint8_t *out_arena,

@@ -191,7 +191,7 @@ def test_few_connections_many_records(shape, dtls, src, monkeypatch, launch_log)
 
 
 # ---- 3. launch shapes with src_off --------------------------------------------------
-# The rules of engine.hip batch() for a grouped batch with a record-size hint
+# The rules of tlsrec_plan.h gcm_plan() / chacha_plan() for a grouped batch with a record-size hint
 # (n records, nkeys loaded keys, rpk = n / nkeys, cu compute units):
 #   one key           8 lanes, 16 waves, once n >= cu * 16 * 8 (Lfill); 4 lanes once
 #                     n >= cu * 16 * 16 and the records are <= 4 KiB

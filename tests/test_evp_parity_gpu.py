@@ -24,50 +24,15 @@ import pytest
 
 import mbedtls_amd as M
 import oracle as O
+from tests.gcmrunlib import EDGE, keys as _keys, layout as _layout, threads as _threads  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-EDGE = np.array([0, 1, 15, 16, 17, 1400, 16383], dtype=np.uint32)
 
 
 def _torch():
     import torch
     assert torch.cuda.is_available(), "needs a GPU"
     return torch
-
-
-def _threads():
-    import bench
-    return bench.host_cores()[0]
-
-
-def _layout(n, head, rng, span=None, misalign=False):
-    """lengths (25 % edge values, 75 % uniform 0..2048, every edge value at
-    least 100 times; or uniform in span), 128-B aligned record buffers with
-    tag / padding room (misalign: each buffer starts 0..127 bytes into its
-    128-B slot)"""
-    if span:
-        lens = rng.integers(span[0], span[1] + 1, n).astype(np.uint32)
-    else:
-        lens = rng.integers(0, 2049, n).astype(np.uint32)
-        pick = rng.random(n) < 0.25
-        lens[pick] = EDGE[rng.integers(0, len(EDGE), int(pick.sum()))]
-        lens[:len(EDGE) * 100] = np.tile(EDGE, 100)
-    size = head + lens.astype(np.uint64) + 48
-    al = (size + 127) // 128 * 128 + (128 if misalign else 0)
-    off = np.zeros(n, dtype=np.uint64)
-    off[1:] = np.cumsum(al)[:-1]
-    if misalign:
-        off += rng.integers(0, 128, n).astype(np.uint64)
-    return lens, size, off, int(off[-1] + al[-1])
-
-
-def _keys(cipher, nkeys, rng):
-    kl = M.KEYLEN[cipher]
-    keys = rng.integers(0, 256, (nkeys, 32), dtype=np.uint8)
-    keys[:, kl:] = 0
-    ivs = rng.integers(0, 256, (nkeys, 12), dtype=np.uint8)
-    return keys, ivs
 
 
 CASES = [(c, v) for c in (M.CIPHER_AES_128_GCM, M.CIPHER_AES_256_GCM, M.CIPHER_CHACHA20_POLY1305)

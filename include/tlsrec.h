@@ -31,7 +31,8 @@
  * ARIA-128/192/256-GCM and -CCM, Camellia-128/192/256-GCM and -CCM;
  * TLS 1.2 and 1.3, and DTLS 1.2 records with an RFC 9146 connection ID) on
  * every entry point, and the TLS 1.2 / DTLS 1.2 AES-128/256-CBC suites with
- * HMAC-SHA1 / -SHA256 / -SHA384, MAC-then-encrypt or encrypt-then-MAC, on the
+ * HMAC-SHA1 / -SHA256 / -SHA384 and the ARIA- and Camellia-128/256-CBC suites
+ * with HMAC-SHA256 / -SHA384, MAC-then-encrypt or encrypt-then-MAC, on the
  * key table, the batch entry points (tlsrec_keytab_load_cbc below) and the
  * _ex forms of the stream and DTLS calls (tlsrec_frame_opts below).
  *
@@ -99,8 +100,17 @@ extern "C" {
  * AES-192-CBC. */
 #define TLSREC_CIPHER_AES_128_CBC        23
 #define TLSREC_CIPHER_AES_256_CBC        24
+/* ARIA-CBC and Camellia-CBC + HMAC (RFC 6209 / RFC 5932 / RFC 6367 TLS 1.2
+ * suites), through the same entry points.  Each id goes with ONE MAC, as every
+ * suite of the reference pairs them: the 128-bit keys with TLSREC_MAC_SHA256,
+ * the 256-bit keys with TLSREC_MAC_SHA384.  No suite uses a 192-bit key here.
+ * Id 25 is no cipher. */
+#define TLSREC_CIPHER_ARIA_128_CBC       26
+#define TLSREC_CIPHER_ARIA_256_CBC       27
+#define TLSREC_CIPHER_CAMELLIA_128_CBC   28
+#define TLSREC_CIPHER_CAMELLIA_256_CBC   29
 #define TLSREC_CIPHER_CBC_FIRST          23
-#define TLSREC_CIPHER_CBC_LAST           24
+#define TLSREC_CIPHER_CBC_LAST           29
 /* record MACs of the CBC suites (no truncated HMAC, no MD5: the reference has
  * neither in a suite); maclen 20 / 32 / 48 */
 #define TLSREC_MAC_SHA1                  1
@@ -460,7 +470,10 @@ typedef struct tlsrec_tls12_conn {
 int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                int prf, const tlsrec_tls12_conn *conns, void *stream);
 
-/* ---- AES-CBC + HMAC slots (TLS 1.2 / DTLS 1.2) ---------------------------
+/* ---- CBC + HMAC slots: AES, ARIA, Camellia (TLS 1.2 / DTLS 1.2) ----------
+ * (ARIA and Camellia: the ids 26..29 above, each with its one MAC; whatever
+ * this section says of a CBC slot holds for them.  Sizes depend on the MAC and
+ * the MAC order only: the block is 16 bytes for all three ciphers.)
  * The MBEDTLS_SSL_MODE_CBC and MBEDTLS_SSL_MODE_CBC_ETM branches of
  * mbedtls_ssl_encrypt_buf / _decrypt_buf (ssl_msg.c:906-968, :1080-1253,
  * :1435-1702, :1717-1801; transform setup ssl_tls.c:7799-7843) for records
@@ -492,16 +505,16 @@ int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count
  *
  * Out of scope: session tickets and the single-record server
  * (tlsrec_encrypt_buf / _decrypt_buf) treat a CBC slot as a slot that was
- * never loaded; ARIA-CBC, Camellia-CBC and the NULL cipher.
+ * never loaded; the NULL cipher.
  * tlsrec_keytab_load, tlsrec_transform_setup, tlsrec_tls12_split_key_block,
  * tlsrec_tls12_make_keys, tlsrec_tls12_keytab_derive, tlsrec_tls13_keytab_derive, tlsrec_stream_out_size
- * and tlsrec_dtls_out_size answer ids 23 and 24 as unknown ciphers. */
+ * and tlsrec_dtls_out_size answer ids 23, 24 and 26..29 as unknown ciphers. */
 
 /* One direction of one connection, 128 bytes. */
 typedef struct tlsrec_cbc_key_material {
-    uint8_t cipher;          /* TLSREC_CIPHER_AES_128_CBC / _256_CBC */
+    uint8_t cipher;          /* TLSREC_CIPHER_AES_128_CBC / _256_CBC, or _ARIA_ / _CAMELLIA_128_CBC / _256_CBC */
     uint8_t tls_minor;       /* 3 (TLS 1.2 / DTLS 1.2) */
-    uint8_t mac;             /* TLSREC_MAC_* */
+    uint8_t mac;             /* TLSREC_MAC_*; ARIA / Camellia: _SHA256 with a 128-bit key, _SHA384 with a 256-bit key */
     uint8_t etm;             /* 0 = MAC-then-encrypt, 1 = encrypt-then-MAC (RFC 7366) */
     uint8_t reserved[44];    /* zero */
     uint8_t key[32];         /* 16 or 32 bytes used */
@@ -512,8 +525,9 @@ typedef struct tlsrec_cbc_key_material {
  * `keys`; host material is staged in a device buffer of the call's own and
  * the call waits for the key setup before it frees it, device material is
  * read once for the checks and the key setup enqueued on `stream`); the GPU expands the AES round keys of both
- * directions and the HMAC inner / outer midstates.  Unknown cipher or mac:
- * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE; tls_minor != 3 or etm > 1:
+ * directions (ARIA, Camellia: the encryption and the decryption key array) and
+ * the HMAC inner / outer midstates.  Unknown cipher or mac, or an ARIA /
+ * Camellia id with another MAC than its suites': TLSREC_ERR_SSL_FEATURE_UNAVAILABLE; tls_minor != 3 or etm > 1:
  * TLSREC_ERR_SSL_BAD_INPUT_DATA.  A slot may be reloaded from AEAD to CBC and
  * back; tlsrec_keytab_set_cid works on a CBC slot (DTLS 1.2 connection IDs). */
 int tlsrec_keytab_load_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count,
@@ -556,11 +570,11 @@ int tlsrec_tls12_make_keys_cbc(int prf, int cipher, int mac, const unsigned char
  * pass through a device staging area of the table (capacity x 128 bytes,
  * allocated by the first call, freed with the table), which is zeroized on
  * `stream` right after the key setup.  A (re)loaded slot has no connection ID.
- * Every (cipher, mac, prf) combination is accepted, as tlsrec_tls12_make_keys_cbc
- * accepts them.  Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for kt
+ * Every (cipher, mac, prf) combination tlsrec_tls12_make_keys_cbc accepts is
+ * accepted (AES with every MAC, ARIA / Camellia with their suites' MAC).  Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for kt
  * NULL, conns NULL with count != 0, or [first, first + 2*count) overflowing or
  * running past the table; TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for an unknown
- * cipher or mac, then for an unknown prf; TLSREC_ERR_SSL_BAD_INPUT_DATA for etm
+ * cipher or mac or a pair no suite has, then for an unknown prf; TLSREC_ERR_SSL_BAD_INPUT_DATA for etm
  * other than 0 or 1.  count == 0 with valid arguments returns 0 and launches
  * nothing. */
 int tlsrec_tls12_keytab_derive_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count,

@@ -58,6 +58,8 @@ TAGLEN = {c: (8 if 8 <= c <= 10 else 16) for c in KEYLEN}
 # AES-CBC + HMAC (key table, batch entry points and the _ex framing calls; mbedtls_amd/cbc.py).
 # Not in KEYLEN / TAGLEN, which list the AEAD ids.
 CIPHER_AES_128_CBC, CIPHER_AES_256_CBC = 23, 24
+# each with one MAC: the 128-bit keys with MAC_SHA256, the 256-bit keys with MAC_SHA384 (25 is no cipher)
+CIPHER_ARIA_128_CBC, CIPHER_ARIA_256_CBC, CIPHER_CAMELLIA_128_CBC, CIPHER_CAMELLIA_256_CBC = 26, 27, 28, 29
 MAC_SHA1, MAC_SHA256, MAC_SHA384 = 1, 2, 3
 MSG_APPLICATION_DATA = 23
 MSG_CID = 25

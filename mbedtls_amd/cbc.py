@@ -18,7 +18,17 @@ from .batch import KeyTable, _stream
 CIPHER_AES_128_CBC = _abi.CIPHER_AES_128_CBC
 CIPHER_AES_256_CBC = _abi.CIPHER_AES_256_CBC
 MAC_SHA1, MAC_SHA256, MAC_SHA384 = _abi.MAC_SHA1, _abi.MAC_SHA256, _abi.MAC_SHA384
-CBC_KEYLEN = {CIPHER_AES_128_CBC: 16, CIPHER_AES_256_CBC: 32}
+CIPHER_ARIA_128_CBC = _abi.CIPHER_ARIA_128_CBC
+CIPHER_ARIA_256_CBC = _abi.CIPHER_ARIA_256_CBC
+CIPHER_CAMELLIA_128_CBC = _abi.CIPHER_CAMELLIA_128_CBC
+CIPHER_CAMELLIA_256_CBC = _abi.CIPHER_CAMELLIA_256_CBC
+CBC_KEYLEN = {CIPHER_AES_128_CBC: 16, CIPHER_AES_256_CBC: 32}           # AES: every MAC
+# ARIA / Camellia: one MAC each, as every suite of the reference pairs them
+CBC_ALT_KEYLEN = {CIPHER_ARIA_128_CBC: 16, CIPHER_ARIA_256_CBC: 32,
+                  CIPHER_CAMELLIA_128_CBC: 16, CIPHER_CAMELLIA_256_CBC: 32}
+CBC_ALL_KEYLEN = {**CBC_KEYLEN, **CBC_ALT_KEYLEN}                       # every id tlsrec_keytab_load_cbc takes
+CBC_ALT_MAC = {CIPHER_ARIA_128_CBC: MAC_SHA256, CIPHER_ARIA_256_CBC: MAC_SHA384,
+               CIPHER_CAMELLIA_128_CBC: MAC_SHA256, CIPHER_CAMELLIA_256_CBC: MAC_SHA384}
 MACLEN = {MAC_SHA1: 20, MAC_SHA256: 32, MAC_SHA384: 48}
 IVLEN = 16
 CBC_KEY_MATERIAL = _abi.CBC_KEY_MATERIAL

@@ -40,17 +40,6 @@ __device__ __forceinline__ uint32_t w4(uint32_t b0, uint32_t b1, uint32_t b2, ui
     return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
 }
 
-/* ARIA: ARIA-CCM / Camellia-CCM (NR = 12/14/16 / 18/24; the S-box image,
- * round keys SlotState::ark) -- the CCM construction around it unchanged */
-template <int NR, bool ARIA, typename RK>
-__device__ __forceinline__ uint4 blk_encrypt(const uint8_t *lds, uint32_t lb, RK rk, uint4 in)
-{
-    if constexpr (ARIA)
-        return alt_encrypt<NR, 0>(lds, lb, rk, in);
-    else
-        return aes_encrypt<NR, 0>(lds, lb, rk, in);
-}
-
 template <int NR, bool DEC, bool CID = false, bool ARIA = false>
 __global__ __launch_bounds__(CCM_THREADS) void tlsrec_ccm_kernel(CcmArgs a)
 {

@@ -64,7 +64,7 @@ extern "C" const char *tlsrec_version_string(void)
 {
     return "tlsrec 0.2 gfx950: aes-128/192/256-gcm(L=4/8/16/64, T-tables in LDS, GHASH 4-bit position tables) "
            "aes-ccm/ccm_8(lane per record) chacha20-poly1305(L=1/2/4/8, 26-bit limbs) "
-           "tls13-key-schedule(hkdf-sha256/384) stream-record-layer aria-128/192/256-gcm/ccm camellia-128/192/256-gcm/ccm dtls1.2-cid dtls1.2-datagram-record-layer(anti-replay) session-tickets aes-128/256-cbc-hmac-sha1/sha256/sha384(mac-then-encrypt, encrypt-then-mac; lane per record)";
+           "tls13-key-schedule(hkdf-sha256/384) stream-record-layer aria-128/192/256-gcm/ccm camellia-128/192/256-gcm/ccm dtls1.2-cid dtls1.2-datagram-record-layer(anti-replay) session-tickets aes-128/256-cbc-hmac-sha1/sha256/sha384(mac-then-encrypt, encrypt-then-mac; lane per record) aria-128/camellia-128-cbc-hmac-sha256 aria-256/camellia-256-cbc-hmac-sha384";
 }
 
 extern "C" int tlsrec_keytab_create(tlsrec_keytab **out, uint32_t capacity)
@@ -154,11 +154,34 @@ extern "C" void tlsrec_keytab_free(tlsrec_keytab *kt)
     free(kt);
 }
 
-static const uint32_t CBC_CIPHER_BITS = (1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC);
+/* the ids cbc_is_cipher() accepts */
+static const uint32_t CBC_CIPHER_BITS = (1u << TLSREC_CIPHER_AES_128_CBC) | (1u << TLSREC_CIPHER_AES_256_CBC) |
+                                        (1u << TLSREC_CIPHER_ARIA_128_CBC) | (1u << TLSREC_CIPHER_ARIA_256_CBC) |
+                                        (1u << TLSREC_CIPHER_CAMELLIA_128_CBC) |
+                                        (1u << TLSREC_CIPHER_CAMELLIA_256_CBC);
+static_assert(TLSREC_CIPHER_CBC_LAST < 32 && 3 * (TLSREC_CIPHER_CBC_LAST - TLSREC_CIPHER_CBC_FIRST) + 2 < 32,
+              "cipher_mask and cbc_variants are 32-bit words");
+/* Key setup of `count` checked CBC records (hk: their host copy, dk: the device copy the kernels read): one
+ * launch per run of records of one kind (AES / ARIA or Camellia), so neither kernel meets the other's material */
+static int launch_cbc_keysetup_runs(tlsrec_keytab *kt, const tlsrec_cbc_key_material *hk,
+                                    const tlsrec_cbc_key_material *dk, uint32_t first, uint32_t count, hipStream_t st)
+{
+    for (uint32_t i = 0; i < count;) {
+        const int alt = cbc_is_alt(hk[i].cipher);
+        uint32_t j = i + 1;
+        while (j < count && cbc_is_alt(hk[j].cipher) == alt) j++;
+        const int r = hip_ok(tlsrec__launch_cbc_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, dk + i, first + i,
+                                                         j - i, alt, st));
+        if (r) return r;
+        i = j;
+    }
+    return 0;
+}
 
-/* A slot that held a CBC key and now gets an AEAD one: its decryption round
- * keys (SlotState::ark) and HMAC midstates (the head of its table area) are
- * not all overwritten by the AEAD key setup, so one kernel zeroizes them,
+/* A slot that held a CBC key and now gets an AEAD one: its round keys of both
+ * directions (SlotState::rk / rkr and ark, whichever way its cipher lays them
+ * out) and HMAC midstates (the head of its table area) are not all
+ * overwritten by the AEAD key setup, so one kernel zeroizes them,
  * enqueued before the key setup (a table that never held a CBC key: nothing). */
 static int wipe_cbc_state(tlsrec_keytab *kt, uint32_t first, uint32_t count, hipStream_t st)
 {
@@ -223,7 +246,8 @@ extern "C" int tlsrec_keytab_load(tlsrec_keytab *kt, uint32_t first, uint32_t co
 
 static int check_cbc_material(const tlsrec_cbc_key_material *k)
 {
-    if (cbc_keylen(k->cipher) == 0 || cbc_maclen(k->mac) == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    /* unknown cipher or MAC, or an ARIA / Camellia id with a MAC no suite pairs it with */
+    if (!cbc_pair_ok(k->cipher, k->mac)) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
     if (k->tls_minor != 3 || k->etm > 1) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     return 0;
 }
@@ -259,7 +283,7 @@ extern "C" int tlsrec_keytab_load_cbc(tlsrec_keytab *kt, uint32_t first, uint32_
     for (uint32_t i = 0; i < count && !r; i++) {
         r = check_cbc_material(&hk[i]);
         if (!r) {
-            variants |= 1u << (3 * (hk[i].cipher - TLSREC_CIPHER_CBC_FIRST) + (hk[i].mac - 1));
+            variants |= cbc_variant_bit(hk[i].cipher, hk[i].mac);
             etm |= 1u << hk[i].etm;
         }
     }
@@ -277,8 +301,7 @@ extern "C" int tlsrec_keytab_load_cbc(tlsrec_keytab *kt, uint32_t first, uint32_
         }
         kt->cbc_variants |= variants;
         kt->cbc_etm |= etm;
-        r = hip_ok(tlsrec__launch_cbc_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, dev ? dev : keys, first, count,
-                                               st));
+        r = launch_cbc_keysetup_runs(kt, hk, dev ? dev : keys, first, count, st);
     }
     if (host) {
         memset(host, 0, bytes);
@@ -349,10 +372,11 @@ extern "C" int tlsrec__keytab_commit_staged_cbc(tlsrec_keytab *kt, uint32_t firs
         kt->h_cipher[first + i] = (uint8_t) cipher;
     }
     kt->cipher_mask |= 1u << cipher;
-    kt->cbc_variants |= 1u << (3 * (cipher - TLSREC_CIPHER_CBC_FIRST) + (mac - 1));
+    kt->cbc_variants |= cbc_variant_bit(cipher, mac);
     kt->cbc_etm |= 1u << etm;
     tlsrec_cbc_key_material *src = kt->d_stage_cbc + first;
-    int r = hip_ok(tlsrec__launch_cbc_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, src, first, count, st));
+    int r = hip_ok(tlsrec__launch_cbc_keysetup(kt->d_slots, kt->d_ghtab, kt->d_cipher, src, first, count,
+                                               cbc_is_alt(cipher), st));
     if (hipMemsetAsync(src, 0, sizeof(*src) * (size_t) count, st) != hipSuccess && r == 0)
         r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     return r;
@@ -849,16 +873,21 @@ static int launch_ccm(const BatchView &v)
     return hip_ok(tlsrec__launch_ccm(&a, v.dec, ccm_nr, v.st));
 }
 
-/* AES-CBC + HMAC: one launch per (key size, MAC) the table holds */
+/* CBC + HMAC: one launch per (cipher, MAC) the table holds */
 static int launch_cbc(const BatchView &v)
 {
     if (!(v.cmask & CBC_CIPHER_BITS)) return 0;
-    uint32_t variants = v.kt->cbc_variants;
-    if (!(v.cmask & (1u << TLSREC_CIPHER_AES_128_CBC))) variants &= ~7u;
-    if (!(v.cmask & (1u << TLSREC_CIPHER_AES_256_CBC))) variants &= 7u;
+    uint32_t variants = v.kt->cbc_variants, macs = 0;
+    for (int c = TLSREC_CIPHER_CBC_FIRST; c <= TLSREC_CIPHER_CBC_LAST; c++) {
+        const uint32_t three = 7u << (3 * (c - TLSREC_CIPHER_CBC_FIRST));     /* the cipher's MACs */
+        if (!(v.cmask & (1u << c))) variants &= ~three;
+        macs |= (variants & three) >> (3 * (c - TLSREC_CIPHER_CBC_FIRST));
+    }
     CbcArgs a = class_args<CbcArgs>(v, BC_CBC);
     a.ghtab = v.kt->d_ghtab;
-    TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC, v.dec, ((variants | (variants >> 3)) & 7u) << 1, v.kt->cbc_etm, 0);
+    /* (p3: the ARIA / Camellia variants, from the bit of ARIA-128 with MAC 1 up; AES alone logs what it always has) */
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC, v.dec, macs << 1, v.kt->cbc_etm,
+                      variants >> (3 * (TLSREC_CIPHER_ARIA_128_CBC - TLSREC_CIPHER_CBC_FIRST)));
     return hip_ok(tlsrec__launch_cbc(&a, v.dec, variants, v.st));
 }
 

@@ -1267,11 +1267,24 @@ extern "C" int tlsrec_tls12_make_keys(int prf, int cipher, const unsigned char m
  * IV in each record, so the IV part of the block goes unused) */
 static size_t cbc_split_keylen(int cipher)
 {
-    return cipher == TLSREC_CIPHER_AES_128_CBC ? 16 : cipher == TLSREC_CIPHER_AES_256_CBC ? 32 : 0;
+    switch (cipher) {
+        case TLSREC_CIPHER_AES_128_CBC: case TLSREC_CIPHER_ARIA_128_CBC: case TLSREC_CIPHER_CAMELLIA_128_CBC: return 16;
+        case TLSREC_CIPHER_AES_256_CBC: case TLSREC_CIPHER_ARIA_256_CBC: case TLSREC_CIPHER_CAMELLIA_256_CBC: return 32;
+        default: return 0;
+    }
 }
 static size_t cbc_split_maclen(int mac)
 {
     return mac == TLSREC_MAC_SHA1 ? 20 : mac == TLSREC_MAC_SHA256 ? 32 : mac == TLSREC_MAC_SHA384 ? 48 : 0;
+}
+/* a pair tlsrec_keytab_load_cbc takes: AES with every MAC, an ARIA / Camellia id
+ * only with its suites' MAC (128-bit keys SHA-256, 256-bit keys SHA-384) */
+static bool cbc_split_pair_ok(int cipher, int mac)
+{
+    const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
+    if (kl == 0 || ml == 0) return false;
+    if (cipher <= TLSREC_CIPHER_AES_256_CBC) return true;
+    return mac == (kl == 16 ? TLSREC_MAC_SHA256 : TLSREC_MAC_SHA384);
 }
 
 extern "C" int tlsrec_tls12_split_key_block_cbc(int cipher, int mac, const unsigned char *keyblk, size_t keyblk_len,
@@ -1279,7 +1292,7 @@ extern "C" int tlsrec_tls12_split_key_block_cbc(int cipher, int mac, const unsig
 {
     if (!out || !keyblk) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
-    if (kl == 0 || ml == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (!cbc_split_pair_ok(cipher, mac)) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
     if (keyblk_len < 2 * ml + 2 * kl) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     memset(out, 0, sizeof(*out));
     tlsrec_cbc_key_material *dir[2] = { &out->client_write, &out->server_write };
@@ -1299,7 +1312,7 @@ extern "C" int tlsrec_tls12_make_keys_cbc(int prf, int cipher, int mac, const un
     const int a = prf_index(prf);
     if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
     const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
-    if (kl == 0 || ml == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (!cbc_split_pair_ok(cipher, mac)) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
     if (!master || !randbytes || !out) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     unsigned char keyblk[160];
     const size_t need = 2 * ml + 2 * kl;
@@ -1410,7 +1423,7 @@ extern "C" int tlsrec__tls12_stage_keys_cbc(tlsrec_keytab *kt, uint32_t first, u
     const uint32_t cap = tlsrec_keytab_capacity(kt);
     if (first > cap || (uint64_t) count * 2 > (uint64_t) (cap - first)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     const size_t kl = cbc_split_keylen(cipher), ml = cbc_split_maclen(mac);
-    if (kl == 0 || ml == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (!cbc_split_pair_ok(cipher, mac)) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
     const int alg = prf_index(prf);
     if (alg < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
     if (etm < 0 || etm > 1) return TLSREC_ERR_SSL_BAD_INPUT_DATA;

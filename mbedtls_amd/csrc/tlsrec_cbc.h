@@ -36,12 +36,51 @@ TLSREC_CBC_HD uint32_t cbc_maclen(int mac)
 }
 TLSREC_CBC_HD uint32_t cbc_keylen(int cipher)
 {
+    return (cipher == TLSREC_CIPHER_AES_128_CBC || cipher == TLSREC_CIPHER_ARIA_128_CBC ||
+            cipher == TLSREC_CIPHER_CAMELLIA_128_CBC) ? 16u
+           : (cipher == TLSREC_CIPHER_AES_256_CBC || cipher == TLSREC_CIPHER_ARIA_256_CBC ||
+              cipher == TLSREC_CIPHER_CAMELLIA_256_CBC) ? 32u : 0u;
+}
+/* (id 25 lies inside [CBC_FIRST, CBC_LAST] and is no cipher) */
+TLSREC_CBC_HD int cbc_is_cipher(int c)
+{
+    return c >= TLSREC_CIPHER_CBC_FIRST && c <= TLSREC_CIPHER_CBC_LAST && c != TLSREC_CIPHER_AES_256_CBC + 1;
+}
+/* AES-CBC alone: the key length, 0 for every other id (the AES record kernels' slot filter) */
+TLSREC_CBC_HD uint32_t cbc_aes_keylen(int cipher)
+{
     return cipher == TLSREC_CIPHER_AES_128_CBC ? 16u : cipher == TLSREC_CIPHER_AES_256_CBC ? 32u : 0u;
 }
-TLSREC_CBC_HD int cbc_is_cipher(int c) { return c >= TLSREC_CIPHER_CBC_FIRST && c <= TLSREC_CIPHER_CBC_LAST; }
+/* ARIA-CBC / Camellia-CBC: the S-box image ciphers (cbc_alt.hip) */
+TLSREC_CBC_HD int cbc_is_alt(int c) { return c >= TLSREC_CIPHER_ARIA_128_CBC && c <= TLSREC_CIPHER_CAMELLIA_256_CBC; }
+/* the round count that picks a slot's record kernel: AES 10 / 14, ARIA 12 / 16
+ * (RFC 5794 2.1), Camellia 18 / 24 (RFC 3713 2.3); 0 for no CBC cipher */
+TLSREC_CBC_HD uint32_t cbc_nr(int c)
+{
+    const uint32_t kl = cbc_keylen(c);
+    if (kl == 0) return 0u;
+    if (c >= TLSREC_CIPHER_CAMELLIA_128_CBC) return kl == 16 ? 18u : 24u;
+    return kl / 4 + (c >= TLSREC_CIPHER_ARIA_128_CBC ? 8u : 6u);
+}
+/* The (cipher, MAC) pairs a slot can hold: AES-CBC with every MAC; ARIA and
+ * Camellia only as the reference's suites pair them (ssl_ciphersuites.c:
+ * 128-bit keys with SHA-256, 256-bit keys with SHA-384). */
+TLSREC_CBC_HD int cbc_pair_ok(int cipher, int mac)
+{
+    if (cbc_keylen(cipher) == 0 || cbc_maclen(mac) == 0) return 0;
+    if (!cbc_is_alt(cipher)) return 1;
+    return mac == (cbc_keylen(cipher) == 16 ? TLSREC_MAC_SHA256 : TLSREC_MAC_SHA384);
+}
+/* bit of a (cipher, MAC) pair in the key table's variants word (tlsrec__launch_cbc) */
+TLSREC_CBC_HD uint32_t cbc_variant_bit(int cipher, int mac)
+{
+    return 1u << (3 * (cipher - TLSREC_CIPHER_CBC_FIRST) + (mac - 1));
+}
 
-/* Per-slot CBC state beyond SlotState (rk / rkr: encryption round keys, ark:
- * decryption round keys, km.reserved[1] = mac, [2] = etm): the HMAC midstates
+/* Per-slot CBC state beyond SlotState (AES: rk / rkr encryption round keys,
+ * ark decryption round keys; ARIA / Camellia the other way round: ark the
+ * encryption keys as in their GCM slots, the decryption key array at the start
+ * of rk / rkr; km.reserved[1] = mac, [2] = etm): the HMAC midstates
  * as 32-bit words at the start of the slot's GHASH table area, which a CBC
  * slot does not otherwise use -- inner at words 0..15, outer at 16..31
  * (SHA-512 words as high, low pairs). */

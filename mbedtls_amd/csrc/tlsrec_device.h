@@ -59,6 +59,8 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
+/* (the host side of __host__ __device__ code: the key schedules of tlsrec_altkey.h) */
+__host__ inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
 
 /* ---------------- LDS T-tables ----------------------------------------- */
 /* Entry x of table j (j = 0: T0 = (2s,s,s,3s), j = 1: T1 = rotl8(T0)),
@@ -416,6 +418,18 @@ __device__ __forceinline__ uint4 alt_encrypt(const uint8_t *lds, uint32_t lb, RK
         return cam_encrypt<NR, OFF>(lds, lb, rk, in);
     else
         return aria_encrypt<NR, OFF>(lds, lb, rk, in);
+}
+
+/* One block under either kind of cipher, for the kernels that serve both (CCM,
+ * CBC): ARIA = the S-box image ciphers (NR = 12/14/16 / 18/24, round keys
+ * SlotState::ark), else AES on the T-tables -- the mode around it unchanged */
+template <int NR, bool ARIA, typename RK>
+__device__ __forceinline__ uint4 blk_encrypt(const uint8_t *lds, uint32_t lb, RK rk, uint4 in)
+{
+    if constexpr (ARIA)
+        return alt_encrypt<NR, 0>(lds, lb, rk, in);
+    else
+        return aes_encrypt<NR, 0>(lds, lb, rk, in);
 }
 
 /* ---------------- GHASH with LDS position tables ----------------------- */

@@ -54,7 +54,9 @@ constexpr int CP_WAVES = CP_THREADS / 64;
 struct SlotState {
     tlsrec_key_material km;   /* raw material as loaded */
     uint32_t rk[60];          /* AES round keys, little-endian column words */
-    uint32_t rkr[60];         /* same, middle rounds 1..NR-1 stored rotr16 (aes_encrypt) */
+    uint32_t rkr[60];         /* same, middle rounds 1..NR-1 stored rotr16 (aes_encrypt).  An ARIA-CBC /
+                                 Camellia-CBC slot has no AES keys: rk and rkr are one run of 120 words whose
+                                 first 68 hold its decryption key array in the layout of ark (tlsrec_altkey.h) */
     uint32_t nr;              /* 10 / 14, 0 for ChaCha20-Poly1305 */
     uint8_t h[16];            /* H = E_K(0^128) */
     uint8_t cid_len;          /* DTLS 1.2 connection ID of this transform direction */
@@ -66,6 +68,7 @@ struct SlotState {
     uint8_t pad[1024 - 64 - 240 - 240 - 4 - 16 - 33 - 3 - 272 - 64];
 };
 static_assert(sizeof(SlotState) == 1024, "SlotState layout");
+static_assert(offsetof(SlotState, rkr) == offsetof(SlotState, rk) + 240, "rk / rkr: one run of 120 words");
 static_assert(sizeof(tlsrec_key_material) == 64, "key material layout");
 static_assert(sizeof(tlsrec_batch_rec) == 40, "batch record layout");
 static_assert(sizeof(tlsrec_batch_res) == 16, "batch result layout");
@@ -185,7 +188,13 @@ hipError_t tlsrec__launch_cbc_wipe(tlsrec::SlotState *slots, uint4 *ghtab, const
                                    uint32_t count, hipStream_t st);
 hipError_t tlsrec__launch_cbc_keysetup(tlsrec::SlotState *slots, uint4 *ghtab, uint8_t *cipher_of,
                                        const tlsrec_cbc_key_material *keys, uint32_t first, uint32_t count,
-                                       hipStream_t st);
+                                       int alt, hipStream_t st);
+/* cbc_alt.hip: the ARIA-CBC / Camellia-CBC record kernels (variants as tlsrec__launch_cbc, grid from it)
+ * and the key setup of their slots */
+hipError_t tlsrec__launch_cbc_alt(const tlsrec::CbcArgs *a, int dec, uint32_t variants, uint32_t grid, hipStream_t st);
+hipError_t tlsrec__launch_cbc_alt_keysetup(tlsrec::SlotState *slots, uint4 *ghtab, uint8_t *cipher_of,
+                                           const tlsrec_cbc_key_material *keys, uint32_t first, uint32_t count,
+                                           hipStream_t st);
 hipError_t tlsrec__launch_ccm(const tlsrec::CcmArgs *a, int dec, uint32_t nr_mask, hipStream_t st);
 hipError_t tlsrec__launch_keysetup(tlsrec::SlotState *slots, uint4 *ghtab, uint8_t *cipher_of,
                                    const tlsrec_key_material *keys,
@@ -219,7 +228,7 @@ void tlsrec__scratch_release(tlsrec_scratch_lease *lease);
 int tlsrec__batch_sized(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res, uint32_t n,
                         const uint8_t *in_arena, uint8_t *out_arena, void *stream, int dec, uint32_t avg_bytes,
                         int prefilled, int cbc);
-/* the table holds (or has held) an AES-CBC slot */
+/* the table holds (or has held) a CBC slot */
 int tlsrec__keytab_has_cbc(const tlsrec_keytab *kt);
 /* encrypt with each record's content read from in_arena + src_off[i] (GcmArgs::
  * src_off) and the records written to out_arena at buf_off: the stream / DTLS
@@ -253,7 +262,9 @@ hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream
  *   CHACHA          p0 lanes per record, p1 src_off set
  *   ALT_GCM / CCM   p0 the cipher / the nr mask
  *   CBC             p0 direction (1 = decrypt), p1 mask of MACs (1 << TLSREC_MAC_*),
- *                   p2 mask of etm values (1 << etm) of the table's CBC slots
+ *                   p2 mask of etm values (1 << etm) of the table's CBC slots,
+ *                   p3 the ARIA / Camellia variants launched: bit 3 * (cipher -
+ *                   TLSREC_CIPHER_ARIA_128_CBC) + (mac - 1), 0 for AES alone
  *   BUCKET          p0 1 = bucket pass taken, 0 = identity order
  *   SEND_FRAME      p0 1 = out_frame_conn_kernel<W> (contents read in place),
  *                   0 = map + send_frame_kernel<W, 64> (copied); p1 1 = DTLS

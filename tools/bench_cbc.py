@@ -3,6 +3,7 @@ the AES-128-CCM batch -- the nearest kernel of the same shape: one lane per
 record, key passes -- timed in the same run at the same record count and size.
 
     python tools/bench_cbc.py [--slots 4096] [--steps 5] [--warmup 2] [--out profiles/r07/rows/cbc.jsonl]
+                                [--ciphers alt]
 
 One JSON line per (variant, record size, direction): GiB/s of record content.
 Decrypt rows read the records the encrypt row of the same variant wrote; both
@@ -27,6 +28,18 @@ VARIANTS = [("cbc128-sha256-mte", C.CIPHER_AES_128_CBC, C.MAC_SHA256, 0),
             ("cbc256-sha384-mte", C.CIPHER_AES_256_CBC, C.MAC_SHA384, 0),
             ("cbc128-sha1-mte", C.CIPHER_AES_128_CBC, C.MAC_SHA1, 0),
             ("ccm128", M.CIPHER_AES_128_CCM, 0, 0)]
+# --ciphers alt: the ARIA / Camellia suites, each beside its yardsticks -- the AES-CBC row of the same MAC and MAC
+# order, and the ARIA- / Camellia-CCM row of the same key size
+ALT_VARIANTS = [("cbc128-sha256-mte", C.CIPHER_AES_128_CBC, C.MAC_SHA256, 0),
+                ("cbc128-sha256-etm", C.CIPHER_AES_128_CBC, C.MAC_SHA256, 1),
+                ("cbc256-sha384-mte", C.CIPHER_AES_256_CBC, C.MAC_SHA384, 0),
+                ("cbc256-sha384-etm", C.CIPHER_AES_256_CBC, C.MAC_SHA384, 1)] + \
+               [("cbc-%s-%s" % (n, "etm" if e else "mte"), c, C.CBC_ALT_MAC[c], e)
+                for n, c in (("aria128-sha256", C.CIPHER_ARIA_128_CBC), ("aria256-sha384", C.CIPHER_ARIA_256_CBC),
+                             ("camellia128-sha256", C.CIPHER_CAMELLIA_128_CBC),
+                             ("camellia256-sha384", C.CIPHER_CAMELLIA_256_CBC)) for e in (0, 1)] + \
+               [("ccm-aria128", M.CIPHER_ARIA_128_CCM, 0, 0), ("ccm-aria256", M.CIPHER_ARIA_256_CCM, 0, 0),
+                ("ccm-camellia128", M.CIPHER_CAMELLIA_128_CCM, 0, 0), ("ccm-camellia256", M.CIPHER_CAMELLIA_256_CCM, 0, 0)]
 SHAPES = [(1400, 65536), (16384, 8192)]    # content bytes, records
 HEAD, ROOM = 16, 16 + 48 + 16              # explicit IV (CCM: 8 of it), MAC / tag and padding
 
@@ -40,7 +53,8 @@ def table(name, cipher, mac, etm, slots, rng):
         km["mac_key"] = rng.integers(0, 256, (slots, 48), dtype=np.uint8)
         C.load(kt, km)
     else:
-        km = np.concatenate([M.key_material(cipher, M.VERSION_TLS1_2, bytes(rng.integers(0, 256, 16, dtype=np.uint8)),
+        km = np.concatenate([M.key_material(cipher, M.VERSION_TLS1_2,
+                                            bytes(rng.integers(0, 256, M.KEYLEN[cipher], dtype=np.uint8)),
                                             bytes(rng.integers(0, 256, 16, dtype=np.uint8))) for _ in range(slots)])
         kt.load(km)
     return kt
@@ -68,12 +82,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default="")
+    ap.add_argument("--ciphers", choices=["aes", "alt"], default="aes",
+                    help="aes: the AES-CBC rows and AES-128-CCM; alt: the ARIA / Camellia suites beside their yardsticks")
     args = ap.parse_args()
     import torch
     dev = torch.device("cuda")
     rng = np.random.default_rng(7)
     rows = []
-    for name, cipher, mac, etm in VARIANTS:
+    for name, cipher, mac, etm in (ALT_VARIANTS if args.ciphers == "alt" else VARIANTS):
         kt = table(name, cipher, mac, etm, args.slots, rng)
         for size, n in SHAPES:
             stride = (HEAD + size + ROOM + 127) // 128 * 128

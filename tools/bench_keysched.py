@@ -241,7 +241,7 @@ def main_tls12_cbc(a):
         ms[name], wall[name] = rowlib.event_timed(fn, a.steps)
     legs["gcm_call"]()          # (the SHA-384 kernel leg staged keys the table never took)
     torch.cuda.synchronize()
-    kl, ml = C.CBC_KEYLEN[cipher], C.MACLEN[mac]
+    kl, ml = C.CBC_ALL_KEYLEN[cipher], C.MACLEN[mac]
     out_len = 2 * ml + 2 * kl
     comp = {"cbc": _compressions(hname, out_len), "gcm": _compressions("sha256", 40), "gcm384": _compressions("sha384", 40)}
     ns = {k: ms[k + "_derive_kernel"] * 1e6 / n / comp[k] for k in comp if k + "_derive_kernel" in ms}

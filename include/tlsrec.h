@@ -126,13 +126,14 @@ extern "C" {
 /* ---- single-record API (host buffers) --------------------------------- */
 
 /* AEAD fields of struct mbedtls_ssl_transform, with raw key bytes and
- * device key-table slots in place of the PSA key ids psa_key_enc/dec. */
+ * device key-table slots in place of the PSA key ids psa_key_enc/dec.  A CBC +
+ * HMAC transform (tlsrec_transform_setup_cbc) uses the same fields. */
 typedef struct tlsrec_transform {
     size_t minlen;           /* min. ciphertext length */
-    size_t ivlen;            /* 12 */
-    size_t fixed_ivlen;      /* 12, or 4 for TLS 1.2 GCM */
-    size_t maclen;           /* 0 for AEAD */
-    size_t taglen;           /* 16 */
+    size_t ivlen;            /* 12; CBC: 16 */
+    size_t fixed_ivlen;      /* 12, or 4 for TLS 1.2 GCM; CBC: 0 */
+    size_t maclen;           /* 0 for AEAD; CBC: 20 / 32 / 48 */
+    size_t taglen;           /* 16; CBC: 0 */
     unsigned char iv_enc[16];
     unsigned char iv_dec[16];
     int tls_version;         /* TLSREC_VERSION_* */
@@ -178,6 +179,30 @@ int tlsrec_transform_setup_ex(tlsrec_transform *t, int tls_version, int cipher,
                               const unsigned char *key_enc, const unsigned char *key_dec,
                               const unsigned char *iv_enc, const unsigned char *iv_dec,
                               unsigned granularity);
+/* The CBC + HMAC branch of ssl_tls12_populate_transform (ssl_tls.c:7798-7847,
+ * keys :7858-7886): cipher a TLSREC_CIPHER_*_CBC id, mac a TLSREC_MAC_*, etm 0
+ * (MAC-then-encrypt) or 1 (encrypt-then-MAC, RFC 7366); key_* point at keylen
+ * bytes, mac_* at maclen (20 / 32 / 48) bytes.  `t` gets ivlen 16, fixed_ivlen
+ * and taglen 0, maclen, minlen = tlsrec_cbc_minlen(mac, etm), the cipher keys;
+ * the MAC keys go into the device key slots only and are kept nowhere on the
+ * host.  tlsrec_transform_set_cid, tlsrec_transform_free, tlsrec_encrypt_buf
+ * and tlsrec_decrypt_buf then work on `t` as on an AEAD transform.
+ * Errors, in this order and before the device is touched:
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA for a NULL pointer, then for a tls_version
+ * other than TLS 1.2; TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for a (cipher, mac)
+ * pair tlsrec_keytab_load_cbc does not accept; TLSREC_ERR_SSL_BAD_INPUT_DATA
+ * for another etm.  Without a device: TLSREC_ERR_SSL_HW_ACCEL_FAILED, `t`
+ * zeroed with both slots -1.
+ *
+ * The explicit IV of an encrypted record: the reference draws it with
+ * psa_generate_random (ssl_msg.c:1124), tlsrec_encrypt_buf draws 16 bytes with
+ * getrandom(2) and writes them at buf + data_offset - 16 (data_offset < 16:
+ * nothing is drawn, the record gets the reference's BUFFER_TOO_SMALL of :1116).
+ * The one divergence: a failed draw returns TLSREC_ERR_SSL_INTERNAL_ERROR, with
+ * the record untouched, where the reference returns the PSA status. */
+int tlsrec_transform_setup_cbc(tlsrec_transform *t, int tls_version, int cipher, int mac, int etm,
+                               const unsigned char *key_enc, const unsigned char *key_dec,
+                               const unsigned char *mac_enc, const unsigned char *mac_dec);
 /* DTLS 1.2 connection IDs of a transform: in_cid (records it decrypts must
  * carry it, else TLSREC_ERR_SSL_UNEXPECTED_CID) and out_cid (records it
  * encrypts get it and become DTLSInnerPlaintext of type TLSREC_MSG_CID) --
@@ -483,7 +508,8 @@ int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count
  * transform.  A batch may mix CBC and AEAD slots freely.
  *
  * The one divergence -- the explicit IV on encrypt: the reference draws it
- * with psa_generate_random (ssl_msg.c:1124); the engine has no RNG.  The
+ * with psa_generate_random (ssl_msg.c:1124); the batch calls have no RNG
+ * (tlsrec_encrypt_buf draws it on the host, above).  The
  * caller places the 16-byte IV at in_arena + buf_off + data_offset - 16 (as
  * the ticket API takes its IV); the engine encrypts under it and writes it to
  * the same offset of out_arena.  data_offset < 16 gives
@@ -503,9 +529,12 @@ int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count
  * Batch key derivation for these suites is tlsrec_tls12_keytab_derive_cbc
  * (below).
  *
- * Out of scope: session tickets and the single-record server
- * (tlsrec_encrypt_buf / _decrypt_buf) treat a CBC slot as a slot that was
- * never loaded; the NULL cipher.
+ * The single-record calls take CBC transforms made by
+ * tlsrec_transform_setup_cbc (above); their records run through the coalescing
+ * launch path, not the resident record server.
+ *
+ * Out of scope: session tickets treat a CBC slot as a slot that was never
+ * loaded; the NULL cipher.
  * tlsrec_keytab_load, tlsrec_transform_setup, tlsrec_tls12_split_key_block,
  * tlsrec_tls12_make_keys, tlsrec_tls12_keytab_derive, tlsrec_tls13_keytab_derive, tlsrec_stream_out_size
  * and tlsrec_dtls_out_size answer ids 23, 24 and 26..29 as unknown ciphers. */

@@ -200,6 +200,7 @@ _VP, _U32, _INT, _SZ = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_
 SIGNATURES = {
     "tlsrec_transform_setup": (_INT, [_VP, _INT, _INT, _VP, _VP, _VP, _VP]),
     "tlsrec_transform_setup_ex": (_INT, [_VP, _INT, _INT, _VP, _VP, _VP, _VP, ctypes.c_uint]),
+    "tlsrec_transform_setup_cbc": (_INT, [_VP, _INT, _INT, _INT, _INT, _VP, _VP, _VP, _VP]),
     "tlsrec_transform_free": (None, [_VP]),
     "tlsrec_transform_set_cid": (_INT, [_VP, _VP, _SZ, _VP, _SZ]),
     "tlsrec_keytab_set_cid": (_INT, [_VP, _U32, _VP, _SZ, _VP]),
@@ -314,6 +315,7 @@ def test_library():
 LOG_GCM, LOG_CHACHA, LOG_ALT_GCM, LOG_CCM, LOG_BUCKET, LOG_SEND_FRAME, LOG_DTLS_RX_FRAME, LOG_STREAM_RX_FRAME = \
     1, 2, 3, 4, 5, 6, 7, 8
 LOG_CBC = 9
+LOG_CBC_KERNEL = 10          # follows every LOG_CBC entry: p0 1 = the wave-per-record kernel, 0 = the lane kernel
 LAUNCH_LOG_ENTRY = np.dtype([("kind", "<i4"), ("p0", "<i4"), ("p1", "<i4"), ("p2", "<i4"), ("p3", "<i4")])
 
 

@@ -64,7 +64,7 @@ extern "C" const char *tlsrec_version_string(void)
 {
     return "tlsrec 0.2 gfx950: aes-128/192/256-gcm(L=4/8/16/64, T-tables in LDS, GHASH 4-bit position tables) "
            "aes-ccm/ccm_8(lane per record) chacha20-poly1305(L=1/2/4/8, 26-bit limbs) "
-           "tls13-key-schedule(hkdf-sha256/384) stream-record-layer aria-128/192/256-gcm/ccm camellia-128/192/256-gcm/ccm dtls1.2-cid dtls1.2-datagram-record-layer(anti-replay) session-tickets aes-128/256-cbc-hmac-sha1/sha256/sha384(mac-then-encrypt, encrypt-then-mac; lane per record) aria-128/camellia-128-cbc-hmac-sha256 aria-256/camellia-256-cbc-hmac-sha384";
+           "tls13-key-schedule(hkdf-sha256/384) stream-record-layer aria-128/192/256-gcm/ccm camellia-128/192/256-gcm/ccm dtls1.2-cid dtls1.2-datagram-record-layer(anti-replay) session-tickets aes-128/256-cbc-hmac-sha1/sha256/sha384(mac-then-encrypt, encrypt-then-mac; lane per record) aria-128/camellia-128-cbc-hmac-sha256 aria-256/camellia-256-cbc-hmac-sha384 cbc-hmac-single-record(decrypt: wave per record)";
 }
 
 extern "C" int tlsrec_keytab_create(tlsrec_keytab **out, uint32_t capacity)
@@ -320,6 +320,15 @@ extern "C" uint32_t tlsrec_cbc_record_len(int mac, int etm, uint32_t content_len
 {
     return cbc_record_len(mac, etm, content_len);
 }
+
+/* what tlsrec_keytab_load_cbc accepts, for the host C of tlsrec_transform_setup_cbc: the key length of an
+ * accepted (cipher, mac) pair, 0 for every other */
+extern "C" uint32_t tlsrec__cbc_pair_keylen(int cipher, int mac)
+{
+    return cbc_pair_ok(cipher, mac) ? cbc_keylen(cipher) : 0u;
+}
+
+extern "C" uint32_t tlsrec__cbc_maclen(int mac) { return cbc_maclen(mac); }
 
 extern "C" uint32_t tlsrec_cbc_minlen(int mac, int etm)
 {
@@ -873,8 +882,10 @@ static int launch_ccm(const BatchView &v)
     return hip_ok(tlsrec__launch_ccm(&a, v.dec, ccm_nr, v.st));
 }
 
-/* CBC + HMAC: one launch per (cipher, MAC) the table holds */
-static int launch_cbc(const BatchView &v)
+/* CBC + HMAC: one launch per (cipher, MAC) the table holds.  The coalesced single-record path decrypts
+ * with a wave per record (cbc_wave.hip; TLSREC_CBC_WAVE=0: the lane kernel there too); encryption, two
+ * dependent chains, and every other batch stay on the lane kernel. */
+static int launch_cbc(const BatchView &v, const BatchOpt &opt, bool wave_knob)
 {
     if (!(v.cmask & CBC_CIPHER_BITS)) return 0;
     uint32_t variants = v.kt->cbc_variants, macs = 0;
@@ -888,6 +899,9 @@ static int launch_cbc(const BatchView &v)
     /* (p3: the ARIA / Camellia variants, from the bit of ARIA-128 with MAC 1 up; AES alone logs what it always has) */
     TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC, v.dec, macs << 1, v.kt->cbc_etm,
                       variants >> (3 * (TLSREC_CIPHER_ARIA_128_CBC - TLSREC_CIPHER_CBC_FIRST)));
+    const bool wave = opt.coalesced && v.dec && wave_knob;
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_CBC_KERNEL, wave, v.dec, 0, 0);
+    if (wave) return hip_ok(tlsrec__launch_cbc_wave(&a, variants, v.st));
     return hip_ok(tlsrec__launch_cbc(&a, v.dec, variants, v.st));
 }
 
@@ -921,6 +935,7 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
     hipStream_t st = (hipStream_t) stream;
     YieldGuard yg(st, !opt.coalesced);
     const GcmKnobs knobs = gcm_knobs_from_env();
+    const bool cbc_wave = plan_env("TLSREC_CBC_WAVE", 1) != 0;
     const uint32_t cmask = (opt.only_mask ? (kt->cipher_mask & opt.only_mask) : kt->cipher_mask) &
                            (opt.no_cbc ? ~CBC_CIPHER_BITS : ~0u);
     BatchView v = { kt, recs, res, n, in, out, st, dec, cmask, g_test_skip, nullptr };
@@ -933,7 +948,7 @@ static int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_b
     if (!rc) rc = launch_aes_gcm(v, opt, knobs, lanes, keyrun);
     if (!rc) rc = launch_alt_gcm(v);
     if (!rc) rc = launch_ccm(v);
-    if (!rc) rc = launch_cbc(v);
+    if (!rc) rc = launch_cbc(v, opt, cbc_wave);
     if (!rc) rc = launch_chacha(v, opt, lanes);
     if (!rc) rc = launch_cbc_refusal(v, opt);
     tlsrec__scratch_release(&bs.lease);
@@ -1270,12 +1285,15 @@ struct Combiner {
 /* A page queues records per (AEAD family, direction): each batch is then one
  * kernel launch, and a call never waits behind another family's kernel --
  * CCM's CBC-MAC is one dependent AES chain per record (a 1.4 KiB record is
- * ~170 us on one lane), GCM and ChaCha20-Poly1305 records take ~25 us. */
-#define ENGINE_QUEUES 6
+ * ~170 us on one lane), GCM and ChaCha20-Poly1305 records take ~25 us.  CBC +
+ * HMAC is a family of its own for the same reason: its hash, and on encrypt
+ * its cipher too, is hundreds of microseconds of dependent work per record. */
+#define ENGINE_QUEUES 8
 static int engine_queue(uint32_t cipher, int dec)
 {
     const int fam = cipher == TLSREC_CIPHER_CHACHA20_POLY1305 ? 1
-                    : (tlsrec_cipher_is_ccm((int) cipher) || tlsrec_cipher_is_alt_ccm((int) cipher)) ? 2 : 0;
+                    : (tlsrec_cipher_is_ccm((int) cipher) || tlsrec_cipher_is_alt_ccm((int) cipher)) ? 2
+                    : cbc_is_cipher((int) cipher) ? 3 : 0;
     return fam * 2 + (dec ? 1 : 0);
 }
 
@@ -1283,6 +1301,7 @@ struct EnginePage {
     tlsrec_keytab *kt;
     uint8_t used[ENGINE_PAGE_SLOTS];
     uint8_t cid[ENGINE_PAGE_SLOTS];      /* the slot has a DTLS connection ID (the record server takes none) */
+    uint8_t etm[ENGINE_PAGE_SLOTS];      /* a CBC slot's MAC order: 1 = encrypt-then-MAC (tlsrec__engine_slot_mac_order) */
     uint32_t nused;
     Combiner *co[ENGINE_QUEUES];
 };
@@ -1342,7 +1361,9 @@ static tlsrec_keytab *slot_table(int slot, uint32_t *idx)
     return g_pages[pg].kt;
 }
 
-extern "C" int tlsrec__engine_slot_alloc(const tlsrec_key_material *km)
+/* A free slot of some page (a new page when every one is full), loaded with km, or with the CBC material ck
+ * when km is NULL */
+static int engine_slot_alloc(const tlsrec_key_material *km, const tlsrec_cbc_key_material *ck)
 {
     pthread_mutex_lock(&g_mu);
     int r = engine_init_locked();
@@ -1376,17 +1397,39 @@ extern "C" int tlsrec__engine_slot_alloc(const tlsrec_key_material *km)
         EnginePage &P = g_pages[pg];
         for (int i = 0; i < ENGINE_PAGE_SLOTS; i++)
             if (!P.used[i]) { slot = i; break; }
-        r = tlsrec_keytab_load(P.kt, (uint32_t) slot, 1, km, 0, g_load);
+        r = km ? tlsrec_keytab_load(P.kt, (uint32_t) slot, 1, km, 0, g_load)
+               : tlsrec_keytab_load_cbc(P.kt, (uint32_t) slot, 1, ck, 0, g_load);
         if (r == 0 && hipStreamSynchronize(g_load) != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         if (r == 0) {
             P.used[slot] = 1;
             P.cid[slot] = 0;
+            P.etm[slot] = km ? 0 : ck->etm;
             P.nused++;
             slot += pg * ENGINE_PAGE_SLOTS;
         }
     }
     pthread_mutex_unlock(&g_mu);
     return r ? r : slot;
+}
+
+extern "C" int tlsrec__engine_slot_alloc(const tlsrec_key_material *km) { return engine_slot_alloc(km, NULL); }
+
+/* The same for a CBC + HMAC slot (tlsrec_transform_setup_cbc).  tlsrec_keytab_load_cbc stages the material in
+ * a device buffer of its own and zeroizes it once the key setup has run: the raw MAC key stays nowhere. */
+extern "C" int tlsrec__engine_slot_alloc_cbc(const tlsrec_cbc_key_material *ck)
+{
+    return ck ? engine_slot_alloc(NULL, ck) : TLSREC_ERR_SSL_BAD_INPUT_DATA;
+}
+
+/* a CBC slot's MAC order: 0 = MAC-then-encrypt, 1 = encrypt-then-MAC; -1 for no slot in use */
+extern "C" int tlsrec__engine_slot_mac_order(int slot)
+{
+    pthread_mutex_lock(&g_mu);
+    uint32_t i = 0;
+    const int r = slot_table(slot, &i) && g_pages[slot / ENGINE_PAGE_SLOTS].used[i]
+                      ? g_pages[slot / ENGINE_PAGE_SLOTS].etm[i] : -1;
+    pthread_mutex_unlock(&g_mu);
+    return r;
 }
 
 extern "C" void tlsrec__engine_slot_free(int slot)
@@ -1397,7 +1440,10 @@ extern "C" void tlsrec__engine_slot_free(int slot)
     EnginePage *P = kt ? &g_pages[slot / ENGINE_PAGE_SLOTS] : NULL;
     if (kt && P->used[i]) {
         /* zeroize (ssl_msg.c:6084-6099); the slot's cipher stays recorded in the
-         * table's mask, so a later batch of this page may launch one kernel more */
+         * table's mask, so a later batch of this page may launch one kernel more.
+         * A CBC slot needs no more than these three: its round keys of both
+         * directions (rk / rkr / ark) lie in the SlotState, its HMAC midstates at
+         * the head of the table area. */
         hipMemsetAsync(kt->d_slots + i, 0, sizeof(SlotState), g_load);
         hipMemsetAsync(kt->d_cipher + i, 0, 1, g_load);
         hipMemsetAsync(kt->d_ghtab + (size_t) i * KEY_TABLE_WORDS, 0, sizeof(uint4) * KEY_TABLE_WORDS, g_load);
@@ -1406,6 +1452,7 @@ extern "C" void tlsrec__engine_slot_free(int slot)
         kt->h_cipher[i] = 0;
         kt->nloaded--;
         P->used[i] = 0;
+        P->etm[i] = 0;
         P->nused--;
     }
     pthread_mutex_unlock(&g_mu);
@@ -1670,6 +1717,24 @@ extern "C" int tlsrec__engine_run(int dec, const tlsrec_batch_rec *rec, unsigned
     pthread_mutex_unlock(&co->mu);
     if (me.rc) return me.rc;
     *out = me.res;
+    return 0;
+}
+
+/* the same for one queue (engine_queue: family * 2 + direction; families GCM, ChaCha20-Poly1305, CCM, CBC) */
+extern "C" int tlsrec__engine_queue_stats(int queue, uint64_t *batches, uint64_t *records)
+{
+    if (queue < 0 || queue >= ENGINE_QUEUES) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    uint64_t b = 0, r = 0;
+    for (int pg = 0; pg < g_npages; pg++) {
+        Combiner *c = g_pages[pg].co[queue];
+        if (!c) continue;
+        pthread_mutex_lock(&c->mu);
+        b += c->batches;
+        r += c->records;
+        pthread_mutex_unlock(&c->mu);
+    }
+    if (batches) *batches = b;
+    if (records) *records = r;
     return 0;
 }
 

@@ -50,6 +50,92 @@ __device__ __forceinline__ uint32_t digest_byte(const uint32_t (&dig)[N], uint32
     return (w >> (24 - 8 * (idx & 3))) & 0xff;
 }
 
+/* The additional data of a record under slot sl (len_field is set by the caller per MAC) */
+__device__ __forceinline__ CbcAad cbc_record_aad(const tlsrec_batch_rec *dp, const SlotState *sl, uint32_t cidl)
+{
+    CbcAad A;
+    A.ctr = dp->ctr;
+    A.cid = sl->cid;
+    A.cid_len = cidl;
+    A.type = dp->type;
+    A.ver0 = dp->ver[0];
+    A.ver1 = dp->ver[1];
+    A.len_field = 0;
+    A.aad_len = cidl ? 23 + cidl : 13;
+    return A;
+}
+
+/* Decryption, the checks before a record byte is used (ssl_msg.c:1302-1320,
+ * :1472-1482, :1503, :1557-1562).  len: data_len on entry; with status 0 the
+ * length of IV || ciphertext (the encrypt-then-MAC tag taken off). */
+__device__ __forceinline__ int32_t cbc_dec_frame(const tlsrec_batch_rec &d, const SlotState *sl, const uint8_t *in,
+                                                 uint32_t cidl, uint32_t etm, uint32_t ML, uint32_t &len)
+{
+    if (d.buf_len < d.data_offset || d.buf_len - d.data_offset < len)          /* :1302-1308 */
+        return TLSREC_E_INTERNAL_ERROR;
+    bool cid_ok = d.cid_len == cidl;                                           /* :1317-1320 */
+    if (cid_ok && cidl) {
+        const uint32_t co = (uint32_t) d.cid_off[0] | ((uint32_t) d.cid_off[1] << 8) |
+                            ((uint32_t) d.cid_off[2] << 16) | ((uint32_t) d.cid_off[3] << 24);
+        const uint8_t *rc = in + d.buf_off + co;
+        for (uint32_t i = 0; i < cidl; i++) cid_ok = cid_ok && rc[i] == sl->cid[i];
+    }
+    if (!cid_ok) return TLSREC_E_UNEXPECTED_CID;
+    if (len < 32 || len < 16 + ML + 1) return TLSREC_E_INVALID_MAC;            /* :1472-1482 */
+    if (etm) len -= ML;                                                        /* :1503 */
+    return (len & 15u) ? TLSREC_E_INVALID_MAC : 0;                             /* :1557-1562 (same result before the MAC) */
+}
+
+/* The padding check of ssl_msg.c:1627-1700 over the plaintext pdst[0, len),
+ * last = its last byte: min(256, len) byte loads, the count of matching bytes
+ * a sum of compares.  Returns len less the padding (less nothing when it is
+ * wrong); correct: 1 / 0. */
+__device__ __forceinline__ uint32_t cbc_check_padding(const uint8_t *pdst, uint32_t len, uint32_t last, uint32_t ML,
+                                                      uint32_t etm, uint32_t &correct)
+{
+    uint32_t padlen = last;                                                    /* :1627 */
+    const uint32_t ge = etm ? (len >= padlen + 1) : (len >= ML + padlen + 1);  /* :1629-1651 */
+    correct = ge;
+    padlen = (ge ? padlen : 0u) + 1;
+    const uint32_t padding_idx = len - padlen;
+    const uint32_t num_checks = len <= 256 ? len : 256;
+    uint32_t pad_count = 0;
+    for (uint32_t idx = len - num_checks; idx < len; idx++)                    /* :1675-1684 */
+        pad_count += (uint32_t) (idx >= padding_idx) & (uint32_t) (pdst[idx] == padlen - 1);
+    correct &= (uint32_t) (pad_count == padlen);
+    padlen = correct ? padlen : 0u;
+    return len - padlen;                                                       /* :1700 */
+}
+
+/* MAC-then-encrypt: the peer's MAC at pdst[L, L + maclen) against dig, L secret
+ * (mbedtls_ct_memcpy_offset + mbedtls_ct_memcmp): maclen + min(256, maxL) byte
+ * loads over [maxL - min(256, maxL), clen); non-zero = they differ */
+template <int N>
+__device__ __forceinline__ uint32_t cbc_peer_mac_diff(const uint8_t *pdst, const uint32_t (&dig)[N], uint32_t L,
+                                                      uint32_t maxL, uint32_t clen)
+{
+    constexpr uint32_t ML = 4 * N;
+    uint32_t diff = 0;
+    const uint32_t minL = maxL > 256 ? maxL - 256 : 0;
+    for (uint32_t j = minL; j < clen; j++) {
+        const uint32_t idx = j - L;
+        const uint32_t x = (uint32_t) pdst[j] ^ digest_byte(dig, idx < ML ? idx : 0u);
+        diff |= idx < ML ? x : 0u;
+    }
+    return diff;
+}
+
+/* ssl_parse_inner_plaintext (:1822-1828) of a record with a connection ID */
+__device__ __forceinline__ int32_t cbc_inner_plaintext(const uint8_t *pdst, uint32_t &len, uint32_t &type)
+{
+    uint32_t n = len;
+    while (n > 0 && pdst[n - 1] == 0) n--;
+    if (n == 0) return TLSREC_E_INVALID_RECORD;
+    type = pdst[n - 1];
+    len = n - 1;
+    return 0;
+}
+
 template <int NR, int MAC, bool DEC>
 __global__ __launch_bounds__(CBC_THREADS) void tlsrec_cbc_kernel(CbcArgs a)
 {
@@ -105,15 +191,7 @@ __global__ __launch_bounds__(CBC_THREADS) void tlsrec_cbc_kernel(CbcArgs a)
         const tlsrec_batch_rec *dp = &a.recs[my_rec];
         const tlsrec_batch_rec d = *dp;
 
-        CbcAad A;
-        A.ctr = dp->ctr;
-        A.cid = sl->cid;
-        A.cid_len = cidl;
-        A.type = d.type;
-        A.ver0 = d.ver[0];
-        A.ver1 = d.ver[1];
-        A.len_field = 0;
-        A.aad_len = cidl ? 23 + cidl : 13;
+        CbcAad A = cbc_record_aad(dp, sl, cidl);
 
         tlsrec_batch_res r;
         r.cid_len = 0;
@@ -193,26 +271,8 @@ __global__ __launch_bounds__(CBC_THREADS) void tlsrec_cbc_kernel(CbcArgs a)
                 if (etm) len += ML;
             }
         } else {
-            uint32_t clen = 0, padlen = 0, correct = 0;
-            if (d.buf_len < off || d.buf_len - off < len) {                        /* :1302-1308 */
-                status = TLSREC_E_INTERNAL_ERROR;
-            } else {
-                bool cid_ok = d.cid_len == cidl;                                   /* :1317-1320 */
-                if (cid_ok && cidl) {
-                    const uint32_t co = (uint32_t) d.cid_off[0] | ((uint32_t) d.cid_off[1] << 8) |
-                                        ((uint32_t) d.cid_off[2] << 16) | ((uint32_t) d.cid_off[3] << 24);
-                    const uint8_t *rc = a.in + d.buf_off + co;
-                    for (uint32_t i = 0; i < cidl; i++) cid_ok = cid_ok && rc[i] == sl->cid[i];
-                }
-                if (!cid_ok) {
-                    status = TLSREC_E_UNEXPECTED_CID;
-                } else if (len < 32 || len < 16 + ML + 1) {                        /* :1472-1482 */
-                    status = TLSREC_E_INVALID_MAC;
-                } else {
-                    if (etm) len -= ML;                                            /* :1503 */
-                    if (len & 15u) status = TLSREC_E_INVALID_MAC;                  /* :1557-1562 (same result before the MAC) */
-                }
-            }
+            uint32_t clen = 0, correct = 0;
+            status = cbc_dec_frame(d, sl, a.in, cidl, etm, ML, len);
             if (!status) {
                 const uint8_t *src = a.in + d.buf_off + d.data_offset;             /* the IV */
                 uint8_t *pdst = a.out + d.buf_off + d.data_offset + 16;            /* the plaintext */
@@ -232,12 +292,7 @@ __global__ __launch_bounds__(CBC_THREADS) void tlsrec_cbc_kernel(CbcArgs a)
                             for (int i = 0; i < H::DIGW; i++) diff |= ld_u32le(src + len + 4 * i) ^ cbc_bswap(dig[i]);
                         } else {
                             len = L;                                               /* :1738 */
-                            const uint32_t minL = maxL > 256 ? maxL - 256 : 0;
-                            for (uint32_t j = minL; j < clen; j++) {               /* mbedtls_ct_memcpy_offset + ct_memcmp */
-                                const uint32_t idx = j - L;
-                                const uint32_t x = (uint32_t) pdst[j] ^ digest_byte(dig, idx < ML ? idx : 0u);
-                                diff |= idx < ML ? x : 0u;
-                            }
+                            diff = cbc_peer_mac_diff(pdst, dig, L, maxL, clen);
                             diff |= correct ^ 1u;
                         }
                         status = diff ? TLSREC_E_INVALID_MAC : 0;
@@ -253,32 +308,11 @@ __global__ __launch_bounds__(CBC_THREADS) void tlsrec_cbc_kernel(CbcArgs a)
                             gstore16(pdst + pos, p);
                         }
                         off += 16;                                                 /* :1572-1573 */
-                        len = clen;
-                        padlen = p.w >> 24;                                        /* :1627 */
-                        const uint32_t ge = etm ? (len >= padlen + 1) : (len >= ML + padlen + 1);   /* :1629-1651 */
-                        correct = ge;
-                        padlen = (ge ? padlen : 0u) + 1;
-                        const uint32_t padding_idx = len - padlen;
-                        const uint32_t num_checks = len <= 256 ? len : 256;
-                        uint32_t pad_count = 0;
-                        for (uint32_t idx = len - num_checks; idx < len; idx++)    /* :1675-1684 */
-                            pad_count += (uint32_t) (idx >= padding_idx) & (uint32_t) (pdst[idx] == padlen - 1);
-                        correct &= (uint32_t) (pad_count == padlen);
-                        padlen = correct ? padlen : 0u;
-                        len -= padlen;                                             /* :1700 */
+                        len = cbc_check_padding(pdst, clen, p.w >> 24, ML, etm, correct);
                         if (etm) status = correct ? 0 : TLSREC_E_INVALID_MAC;
                     }
                 }
-                if (!status && cidl) {                                             /* ssl_parse_inner_plaintext, :1822-1828 */
-                    uint32_t n = len;
-                    while (n > 0 && pdst[n - 1] == 0) n--;
-                    if (n == 0) {
-                        status = TLSREC_E_INVALID_RECORD;
-                    } else {
-                        type = pdst[n - 1];
-                        len = n - 1;
-                    }
-                }
+                if (!status && cidl) status = cbc_inner_plaintext(pdst, len, type);
             }
         }
         r.status = status;

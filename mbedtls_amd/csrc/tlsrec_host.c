@@ -8,9 +8,16 @@
  * record bytes are decided here with the same framing plan the kernels use
  * (tlsrec_frame.h); everything else -- the AEAD, the tag check, the TLS 1.3
  * unpadding -- runs on the GPU through the batch kernels with a batch of one.
+ *
+ * A CBC + HMAC transform (tlsrec_transform_setup_cbc) has no host-side plan:
+ * the CBC kernels carry the framing checks of their branches and the statuses
+ * that go with them, so its records go to the engine as they are.  The one
+ * thing the host adds is the explicit IV of an encrypted record.
  */
+#include <errno.h>
 #include <stdint.h>
 #include <string.h>
+#include <sys/random.h>
 
 #include "tlsrec.h"
 #include "tlsrec_frame.h"
@@ -21,6 +28,9 @@ void tlsrec__engine_slot_free(int slot);
 int tlsrec__engine_run(int dec, const tlsrec_batch_rec *rec, unsigned char *buf, size_t buf_len,
                        const unsigned char *cid, const void *plan, tlsrec_batch_res *out);
 int tlsrec__engine_slot_set_cid(int slot, const unsigned char *cid, size_t cid_len);
+int tlsrec__engine_slot_alloc_cbc(const tlsrec_cbc_key_material *km);
+uint32_t tlsrec__cbc_pair_keylen(int cipher, int mac);
+uint32_t tlsrec__cbc_maclen(int mac);
 
 static void zeroize(void *p, size_t n)
 {
@@ -97,6 +107,61 @@ int tlsrec_transform_setup_ex(tlsrec_transform *t, int tls_version, int cipher,
     return 0;
 }
 
+/* The CBC branch of ssl_tls12_populate_transform (ssl_tls.c:7798-7847, keys
+ * :7858-7886).  The MAC keys go to the device slots and nowhere else: the
+ * transform has no field for them, and the staged material is zeroized here
+ * and in tlsrec_keytab_load_cbc.  The MAC id follows from maclen; the engine
+ * keeps each slot's MAC order (tlsrec__engine_slot_mac_order). */
+int tlsrec_transform_setup_cbc(tlsrec_transform *t, int tls_version, int cipher, int mac, int etm,
+                               const unsigned char *key_enc, const unsigned char *key_dec,
+                               const unsigned char *mac_enc, const unsigned char *mac_dec)
+{
+    if (t == NULL || key_enc == NULL || key_dec == NULL || mac_enc == NULL || mac_dec == NULL)
+        return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (tls_version != TLSREC_VERSION_TLS1_2) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const uint32_t keylen = tlsrec__cbc_pair_keylen(cipher, mac);
+    if (keylen == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (etm != 0 && etm != 1) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    memset(t, 0, sizeof(*t));
+    t->slot_enc = t->slot_dec = -1;
+    t->granularity = TLSREC_PADDING_GRANULARITY;
+    t->cipher = cipher;
+    t->tls_version = tls_version;
+    t->keylen = keylen;
+    t->ivlen = 16;                                         /* ssl_tls.c:7812 (the block size) */
+    t->fixed_ivlen = 0;
+    t->taglen = 0;
+    t->maclen = tlsrec__cbc_maclen(mac);
+    t->minlen = tlsrec_cbc_minlen(mac, etm);               /* :7822-7835 */
+    memcpy(t->key_enc, key_enc, keylen);
+    memcpy(t->key_dec, key_dec, keylen);
+
+    tlsrec_cbc_key_material km;
+    memset(&km, 0, sizeof(km));
+    km.cipher = (uint8_t) cipher;
+    km.tls_minor = 3;
+    km.mac = (uint8_t) mac;
+    km.etm = (uint8_t) etm;
+    memcpy(km.key, key_enc, keylen);
+    memcpy(km.mac_key, mac_enc, t->maclen);
+    int r = tlsrec__engine_slot_alloc_cbc(&km);
+    if (r >= 0) {
+        t->slot_enc = r;
+        memcpy(km.key, key_dec, keylen);
+        memcpy(km.mac_key, mac_dec, t->maclen);
+        r = tlsrec__engine_slot_alloc_cbc(&km);
+        if (r >= 0) t->slot_dec = r;
+    }
+    zeroize(&km, sizeof(km));
+    if (r < 0) {
+        if (t->slot_enc >= 0) tlsrec__engine_slot_free(t->slot_enc);
+        zeroize(t, sizeof(*t));
+        t->slot_enc = t->slot_dec = -1;
+        return r;
+    }
+    return 0;
+}
+
 /* transform->in_cid / out_cid (ssl_tls12_populate_transform, library/ssl_tls.c);
  * the encrypt slot gets out_cid, the decrypt slot in_cid */
 int tlsrec_transform_set_cid(tlsrec_transform *t, const unsigned char *in_cid, size_t in_len,
@@ -169,13 +234,77 @@ static int run(int dec, tlsrec_transform *t, tlsrec_record *rec, const tlsrec_pl
     return res.status;
 }
 
-/* mbedtls_ssl_encrypt_buf (ssl_msg.c:784-1268), AEAD transforms */
+static int is_cbc(const tlsrec_transform *t)
+{
+    return t->cipher >= TLSREC_CIPHER_CBC_FIRST && t->cipher <= TLSREC_CIPHER_CBC_LAST;
+}
+
+/* the record lies inside its buffer (ssl_msg.c:814-823, :1302-1308): the first
+ * check of the CBC kernels too, made here so that a data_offset or data_len
+ * beyond 32 bits never reaches their 32-bit descriptor */
+static int rec_in_buf(const tlsrec_record *rec)
+{
+    return rec->buf_len >= rec->data_offset && rec->buf_len - rec->data_offset >= rec->data_len;
+}
+
+#ifdef TLSREC_TEST_HOOKS
+/* test hook: the explicit IV of every CBC record encrypted from now on (NULL: drawn again) */
+static unsigned char g_pin_iv[16];
+static volatile int g_pin_iv_set = 0;
+void tlsrec__test_pin_cbc_iv(const unsigned char *iv)
+{
+    g_pin_iv_set = 0;
+    if (iv) {
+        memcpy(g_pin_iv, iv, 16);
+        g_pin_iv_set = 1;
+    }
+}
+#endif
+
+/* The explicit IV of a CBC record (ssl_msg.c:1124 draws it with
+ * psa_generate_random): 16 bytes from getrandom(2). */
+static int draw_iv(unsigned char iv[16])
+{
+#ifdef TLSREC_TEST_HOOKS
+    if (g_pin_iv_set) {
+        memcpy(iv, g_pin_iv, 16);
+        return 0;
+    }
+#endif
+    size_t have = 0;
+    while (have < 16) {
+        const ssize_t n = getrandom(iv + have, 16 - have, 0);
+        if (n < 0 && errno == EINTR) continue;
+        if (n <= 0) return -1;
+        have += (size_t) n;
+    }
+    return 0;
+}
+
+/* mbedtls_ssl_encrypt_buf (ssl_msg.c:784-1268) */
 int tlsrec_encrypt_buf(void *ssl, tlsrec_transform *t, tlsrec_record *rec)
 {
     (void) ssl;   /* debug-only in the reference (ssl_msg.c:802-806) */
     if (t == NULL) return TLSREC_ERR_SSL_INTERNAL_ERROR;                       /* :810-813 */
     if (rec == NULL || rec->buf == NULL) return TLSREC_ERR_SSL_INTERNAL_ERROR; /* :814-823 */
     if (rec->buf_len > 0xffffffffu) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (is_cbc(t)) {
+        /* MBEDTLS_SSL_MODE_CBC / _CBC_ETM: every further check and status is the kernel's (cbc.hip) */
+        if (!rec_in_buf(rec) || t->slot_enc < 0) return TLSREC_ERR_SSL_INTERNAL_ERROR;
+        unsigned char iv[16], given[16];
+        unsigned char *ivp = rec->data_offset >= 16 ? rec->buf + rec->data_offset - 16 : NULL;
+        if (ivp) {                               /* else the kernel's :1116 check answers */
+            if (draw_iv(iv) != 0) return TLSREC_ERR_SSL_INTERNAL_ERROR;   /* nothing touched */
+            memcpy(given, ivp, 16);
+            memcpy(ivp, iv, 16);
+        }
+        const int r = run(0, t, rec, NULL);
+        /* no kernel reached the record (run() left rec alone): the buffer as given, too */
+        if (ivp && (r == TLSREC_ERR_SSL_INTERNAL_ERROR || r == TLSREC_ERR_SSL_ALLOC_FAILED ||
+                    r == TLSREC_ERR_SSL_HW_ACCEL_FAILED))
+            memcpy(ivp, given, 16);
+        return r;
+    }
     tlsrec_plan_key k = pkey(t, 0);
     tlsrec_plan p;
     tlsrec_plan_encrypt(&p, &k, rec->ctr, rec->type, rec->ver, rec->buf_len, rec->data_offset,
@@ -198,7 +327,7 @@ int tlsrec_encrypt_buf(void *ssl, tlsrec_transform *t, tlsrec_record *rec)
     return run(0, t, rec, &p);
 }
 
-/* mbedtls_ssl_decrypt_buf (ssl_msg.c:1270-1834), AEAD transforms */
+/* mbedtls_ssl_decrypt_buf (ssl_msg.c:1270-1834) */
 int tlsrec_decrypt_buf(const void *ssl, tlsrec_transform *t, tlsrec_record *rec)
 {
     (void) ssl;
@@ -208,6 +337,10 @@ int tlsrec_decrypt_buf(const void *ssl, tlsrec_transform *t, tlsrec_record *rec)
     tlsrec_plan_key k = pkey(t, 1);
     tlsrec_plan p;
     if (rec->cid_len > TLSREC_CID_LEN_MAX) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (is_cbc(t)) {
+        if (!rec_in_buf(rec) || t->slot_dec < 0) return TLSREC_ERR_SSL_INTERNAL_ERROR;
+        return run(1, t, rec, NULL);
+    }
     tlsrec_plan_decrypt(&p, &k, rec->ctr, rec->type, rec->ver, rec->buf_len, rec->data_offset, rec->data_len,
                         rec->cid, rec->cid_len);
     if (p.status != 0) {

@@ -189,6 +189,8 @@ hipError_t tlsrec__launch_cbc_wipe(tlsrec::SlotState *slots, uint4 *ghtab, const
 hipError_t tlsrec__launch_cbc_keysetup(tlsrec::SlotState *slots, uint4 *ghtab, uint8_t *cipher_of,
                                        const tlsrec_cbc_key_material *keys, uint32_t first, uint32_t count,
                                        int alt, hipStream_t st);
+/* cbc_wave.hip: decryption with a wave per record, identity order (the coalesced single-record path) */
+hipError_t tlsrec__launch_cbc_wave(const tlsrec::CbcArgs *a, uint32_t variants, hipStream_t st);
 /* cbc_alt.hip: the ARIA-CBC / Camellia-CBC record kernels (variants as tlsrec__launch_cbc, grid from it)
  * and the key setup of their slots */
 hipError_t tlsrec__launch_cbc_alt(const tlsrec::CbcArgs *a, int dec, uint32_t variants, uint32_t grid, hipStream_t st);
@@ -265,6 +267,8 @@ hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream
  *                   p2 mask of etm values (1 << etm) of the table's CBC slots,
  *                   p3 the ARIA / Camellia variants launched: bit 3 * (cipher -
  *                   TLSREC_CIPHER_ARIA_128_CBC) + (mac - 1), 0 for AES alone
+ *   CBC_KERNEL      follows every CBC entry: p0 1 = the wave-per-record kernel (cbc_wave.hip), 0 = the
+ *                   lane kernel; p1 direction
  *   BUCKET          p0 1 = bucket pass taken, 0 = identity order
  *   SEND_FRAME      p0 1 = out_frame_conn_kernel<W> (contents read in place),
  *                   0 = map + send_frame_kernel<W, 64> (copied); p1 1 = DTLS
@@ -282,7 +286,8 @@ enum {
     TLSREC_LOG_SEND_FRAME = 6,
     TLSREC_LOG_DTLS_RX_FRAME = 7,
     TLSREC_LOG_STREAM_RX_FRAME = 8,
-    TLSREC_LOG_CBC = 9
+    TLSREC_LOG_CBC = 9,
+    TLSREC_LOG_CBC_KERNEL = 10
 };
 #ifdef TLSREC_TEST_HOOKS
 extern "C" void tlsrec__test_launch_log_add(int32_t kind, int32_t p0, int32_t p1, int32_t p2, int32_t p3);

@@ -3,7 +3,8 @@
     Transform  ~ struct mbedtls_ssl_transform, populated like
                  mbedtls_ssl_tls13_populate_transform (ssl_tls13_keys.c:922)
                  / the AEAD branch of ssl_tls12_populate_transform
-                 (ssl_tls.c:7768-7797)
+                 (ssl_tls.c:7768-7797); Transform.cbc: its CBC + HMAC
+                 branch (ssl_tls.c:7798-7847)
     Record     ~ mbedtls_record (ssl_misc.h:1163-1188), incl. the DTLS 1.2
                  connection ID (cid)
     encrypt_buf(transform, rec)  ~ mbedtls_ssl_encrypt_buf (ssl_msg.c:784)
@@ -53,6 +54,23 @@ class Transform:
         if r != 0:
             raise RuntimeError(f"tlsrec_transform_setup failed: {r:#x}")
         self.tls_version, self.cipher = tls_version, cipher
+
+    @classmethod
+    def cbc(cls, tls_version: int, cipher: int, mac: int, etm: int, key_enc: bytes, key_dec: bytes,
+            mac_enc: bytes, mac_dec: bytes) -> "Transform":
+        """A CBC + HMAC transform (tlsrec_transform_setup_cbc): cipher a CIPHER_*_CBC id, mac a
+        MAC_*, etm 0 = MAC-then-encrypt / 1 = encrypt-then-MAC.  encrypt_buf draws the explicit
+        IV itself and writes it in front of the content."""
+        self = cls.__new__(cls)
+        self._lib = _abi.load()
+        self._t = _abi.CTransform()
+        r = self._lib.tlsrec_transform_setup_cbc(ctypes.byref(self._t), tls_version, cipher, mac, etm,
+                                                 bytes(key_enc), bytes(key_dec), bytes(mac_enc), bytes(mac_dec))
+        if r != 0:
+            self._t = None
+            raise RuntimeError(f"tlsrec_transform_setup_cbc failed: {r:#x}")
+        self.tls_version, self.cipher = tls_version, cipher
+        return self
 
     def set_cid(self, in_cid: bytes, out_cid: bytes) -> None:
         """transform->in_cid / out_cid (DTLS 1.2 connection IDs)."""

@@ -195,6 +195,34 @@ def chacha_plan(n, cu, lanes_in, has_cid):
     return out
 
 
+class FrameKnobs(ctypes.Structure):
+    """tlsrec::FrameKnobs: the TLSREC_RX_* / TLSREC_DTLS_STASH / TLSREC_STREAM_SRC switches"""
+    _fields_ = [("groupwalk", _U32), ("fused_stream", _U32), ("rg", _I32), ("fused", _U32), ("stash", _U32),
+                ("prefill", _U32), ("mailbox", _U32), ("stream_src", _U32)]
+
+
+class StreamRxPlan(ctypes.Structure):
+    _fields_ = [(f, _I32 if f == "G" else _U32) for f in ("fused", "G", "tile", "tiles", "count_grid", "emit_grid")]
+
+
+class DtlsRxPlan(ctypes.Structure):
+    _fields_ = [("fused", _U32), ("S", _I32), ("tiles", _U32)]
+
+
+def _rx_plan(name, out):
+    """tlsrec__stream_rx_plan / tlsrec__dtls_rx_plan; knobs None = the process environment's switches"""
+    def plan(a, b, knobs=None):
+        f, o = getattr(load(), name), out()
+        f.restype, f.argtypes = None, [_U32, _U32, ctypes.c_void_p, ctypes.c_void_p]
+        f(a, b, ctypes.byref(knobs) if knobs is not None else None, ctypes.byref(o))
+        return o
+    return plan
+
+
+stream_rx_plan = _rx_plan("tlsrec__stream_rx_plan", StreamRxPlan)     # (nstreams, max_records, knobs=None)
+dtls_rx_plan = _rx_plan("tlsrec__dtls_rx_plan", DtlsRxPlan)           # (nconns, ndgrams, knobs=None)
+
+
 # every function include/tlsrec.h declares, with its signature
 _VP, _U32, _INT, _SZ = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
 SIGNATURES = {

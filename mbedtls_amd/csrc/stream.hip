@@ -34,8 +34,12 @@
 #include "tlsrec_cbc.h"
 #include "tlsrec_frame.h"
 #include "tlsrec_internal.h"
+#include "tlsrec_plan.h"
 
+using tlsrec::DtlsRxPlan;
+using tlsrec::FrameKnobs;
 using tlsrec::SlotState;
+using tlsrec::StreamRxPlan;
 using tlsrec::cbc_body_len;
 using tlsrec::cbc_is_cipher;
 using tlsrec::cbc_maclen;
@@ -141,48 +145,6 @@ struct HdrStop {
     uint32_t pos;
 };
 
-/* Walk one connection's headers (ssl_parse_record_header + fetch_input);
- * f(k, pos, type, ver, dlen) for each complete record; lim = the header + body
- * limit of the connection's slot kind (rx_limit). */
-template <typename F>
-__device__ HdrStop walk_in(const uint8_t *base, uint32_t len, uint32_t lim, F f)
-{
-    uint32_t pos = 0, k = 0;
-    HdrStop st = { 0, 0 };
-    while (len - pos >= 5) {
-        const uint8_t *h = base + pos;
-        const uint32_t type = h[0], ver = ((uint32_t) h[1] << 8) | h[2], dlen = ((uint32_t) h[3] << 8) | h[4];
-        if (type < 20 || type > 23) { st.status = TLSREC_ERR_SSL_INVALID_RECORD; break; }   /* :3529-3539 */
-        if (ver > (uint32_t) MAX_VERSION) { st.status = TLSREC_ERR_SSL_INVALID_RECORD; break; }
-        if (dlen == 0) { st.status = TLSREC_ERR_SSL_INVALID_RECORD; break; }                /* :3723-3726 */
-        if (5 + dlen > lim) { st.status = TLSREC_ERR_SSL_BAD_INPUT_DATA; break; }
-        if (len - pos < 5 + dlen) break;                                                     /* wait */
-        f(k, pos, type, h[1], h[2], dlen);
-        k++;
-        pos += 5 + dlen;
-    }
-    st.pos = pos;
-    return st;
-}
-
-template <bool CBC>
-__global__ void in_count_kernel(const tlsrec_stream_in *s, uint32_t n, const uint8_t *arena, const SlotState *slots,
-                                uint32_t cap, uint32_t *counts, HdrStop *stops, unsigned long long *bytes)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long b = 0;
-    if (i < n) {
-        uint32_t c = 0;
-        const HdrStop st = walk_in(arena + s[i].off, s[i].len, rx_limit<CBC>(slots, cap, s[i].slot),
-                                   [&](uint32_t, uint32_t, uint32_t, uint8_t, uint8_t, uint32_t dlen) { c++; b += dlen; });
-        counts[i] = c;
-        stops[i] = st;
-    } else if (i == n) {                /* scan sentinel: offs[n] = total */
-        counts[n] = 0;
-    }
-    wave_add_bytes(bytes, b);
-}
-
 /* the descriptor of the record whose header (type, v0 v1, dlen) is at pos,
  * with sequence number seq */
 __device__ __forceinline__ tlsrec_batch_rec rx_desc(const tlsrec_stream_in &si, bool tls13, uint32_t pos, uint32_t type,
@@ -200,29 +162,6 @@ __device__ __forceinline__ tlsrec_batch_rec rx_desc(const tlsrec_stream_in &si, 
     d.ver[0] = v0;
     d.ver[1] = v1;
     return d;
-}
-
-template <bool CBC>
-__global__ void in_emit_kernel(const tlsrec_stream_in *s, uint32_t n, const uint8_t *arena, const uint32_t *offs,
-                               const SlotState *slots, uint32_t cap, tlsrec_batch_rec *recs, uint32_t max_records,
-                               tlsrec_batch_res *res)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const tlsrec_stream_in si = s[i];
-    const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
-    uint64_t seq = be64(si.in_ctr);
-    tlsrec_batch_rec *out = recs + offs[i];
-    const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
-    walk_in(arena + si.off, si.len, lim,
-            [&](uint32_t k, uint32_t pos, uint32_t type, uint8_t v0, uint8_t v1, uint32_t dlen) {
-        const tlsrec_batch_rec d = rx_desc(si, tls13, pos, type, v0, v1, dlen, seq);
-        if (!(tls13 && type == 20)) seq++;                  /* (a TLS 1.3 CCS takes no number) */
-        if (offs[i] + k < max_records) {                /* (launched before the host has checked the total) */
-            out[k] = d;
-            guard_result(&res[offs[i] + k]);
-        }
-    });
 }
 
 template <bool CBC>
@@ -303,23 +242,20 @@ __global__ void in_finish_kernel(const tlsrec_stream_in *s, uint32_t n, const ui
     sres[i] = o;
 }
 
-/* ---------------- receive, lane-group framing (r06) ---------------------
- * in_count_kernel / in_emit_kernel with RG lanes per connection (a group)
- * instead of one: the header walk of walk_in, speculatively parallel -- from
- * position p the group's lanes j read the header a run of equal-length
- * records would put at p + j (5 + dlen0), dlen0 the length of the header at
- * p; the leading lanes whose headers pass walk_in's checks with that length
- * are records (each one's predecessor is a record of length dlen0), the
- * first that does not is where the next round starts.  The same records and
- * the same stop as the serial walk; a stream of full-size records takes
- * ceil(records / RG) rounds of two dependent loads, where one lane per
- * connection took a serial chain of one dependent load per record (1 M
- * headers of 64 K connections: 16 loads in a row per lane, 4 waves per CU).
- * (A single-pass form with a decoupled look-back over 16-connection tiles
- * measured 7 ms for 256 K connections: thread 0's serial look-back over
- * tiles that had published only their aggregates; not kept) */
+/* ---------------- receive framing: the header walk -----------------------
+ * A connection's headers are walked by a group of G lanes (r06; r05 walked
+ * with one), speculatively parallel -- from position p the group's lanes j
+ * read the header a run of equal-length records would put at p + j (5 +
+ * dlen0), dlen0 the length of the header at p; the leading lanes whose
+ * headers pass rx_header's checks with that length are records (each one's
+ * predecessor is a record of length dlen0), the first that does not is where
+ * the next round starts.  The same records and the same stop as a serial
+ * walk; a stream of full-size records takes ceil(records / G) rounds of two
+ * dependent loads, where one lane per connection takes a serial chain of one
+ * dependent load per record (1 M headers of 64 K connections: 16 loads in a
+ * row per lane, 4 waves per CU).  G = 1 is that serial walk (TLSREC_RX_GROUPWALK=0). */
 constexpr int RG = 16;                         /* lanes per connection */
-constexpr int RX_THREADS = 256;
+constexpr int RX_THREADS = tlsrec::PLAN_RX_THREADS;
 constexpr int RX_CONNS = RX_THREADS / RG;      /* connections per workgroup */
 
 /* the group's G bits of a wave ballot (group-uniform control flow) */
@@ -335,7 +271,8 @@ struct RxHdr {
     uint8_t v0, v1;
 };
 
-/* the header at q checked as walk_in does (lim: its limit), and of length want */
+/* the header at q checked as ssl_parse_record_header does (lim: rx_limit, the
+ * fetch_input size limit), and of length want -- the only TLS header check */
 __device__ __forceinline__ RxHdr rx_header(const uint8_t *base, uint32_t len, uint64_t q, uint32_t want, uint32_t lim,
                                            int32_t *err)
 {
@@ -357,9 +294,9 @@ __device__ __forceinline__ RxHdr rx_header(const uint8_t *base, uint32_t len, ui
     return h;
 }
 
-/* walk_in with the group: f(k, h, ccs_before) on the lane holding record k,
- * ccs_before = the TLS 1.3 CCS records before it (tls13 only: they take no
- * sequence number).  Returns the stop and the record count (group-uniform). */
+/* One connection's headers walked by its group: f(k, h, ccs_before) on the lane holding record k, ccs_before =
+ * the TLS 1.3 CCS records before it (tls13 only: they take no sequence number).  Returns the stop and the
+ * record count (group-uniform). */
 template <int G = RG, typename F>
 __device__ HdrStop group_walk(const uint8_t *base, uint32_t len, int lane, bool tls13, uint32_t lim, uint32_t *count,
                               F f)
@@ -389,9 +326,43 @@ __device__ HdrStop group_walk(const uint8_t *base, uint32_t len, int lane, bool 
     return st;
 }
 
-/* G lanes per connection: 16, or 4 / 8 when the caller's max_records says
- * connections hold that few records (r06: a 4-record stream left 12 of 16
- * lanes idle, four times the waves the walk needed) */
+/* Connection si counted by its G lanes: the records (group-uniform), *st how
+ * the walk stopped; the lane's own records' content bytes are added to *b. */
+template <int G, bool CBC>
+__device__ __forceinline__ uint32_t rx_count_conn(const tlsrec_stream_in si, const uint8_t *arena,
+                                                  const SlotState *slots, uint32_t cap, int lane, HdrStop *st,
+                                                  unsigned long long *b)
+{
+    uint32_t cnt = 0;
+    *st = group_walk<G>(arena + si.off, si.len, lane, false, rx_limit<CBC>(slots, cap, si.slot), &cnt,
+                        [&](uint32_t, const RxHdr &h, uint32_t) { *b += h.dlen; });
+    return cnt;
+}
+
+/* Connection si's descriptors, by its G lanes, to recs[off ...], the guard's result beside each; none from max_records
+ * on (launched before the host has checked the total).  off by reference: the emit kernel's is offs[i], read per record. */
+template <int G, bool CBC>
+__device__ __forceinline__ void rx_emit_conn(const tlsrec_stream_in si, const uint8_t *arena, const SlotState *slots,
+                                             uint32_t cap, int lane, const uint32_t &off, tlsrec_batch_rec *recs,
+                                             uint32_t max_records, tlsrec_batch_res *res)
+{
+    const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
+    const uint64_t seq0 = be64(si.in_ctr);
+    tlsrec_batch_rec *out = recs + off;
+    const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
+    uint32_t cnt;
+    group_walk<G>(arena + si.off, si.len, lane, tls13, lim, &cnt, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
+        /* in_ctr + the records before that took a number (a TLS 1.3 CCS takes none) */
+        const tlsrec_batch_rec d = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
+        if (off + k < max_records) {
+            out[k] = d;
+            guard_result(&res[off + k]);
+        }
+    });
+}
+
+/* Count and emit kernels, RX_THREADS / G connections per workgroup.  G: 16, 4 / 8 when the caller's max_records
+ * says connections hold that few records, 1 with TLSREC_RX_GROUPWALK=0 (stream_rx_plan, tlsrec_plan.h). */
 template <int G, bool CBC>
 __global__ __launch_bounds__(RX_THREADS) void in_count_group_kernel(const tlsrec_stream_in *s, uint32_t n,
                                                                     const uint8_t *arena, const SlotState *slots,
@@ -403,9 +374,8 @@ __global__ __launch_bounds__(RX_THREADS) void in_count_group_kernel(const tlsrec
     unsigned long long b = 0;
     if (i < n) {
         const tlsrec_stream_in si = s[i];
-        uint32_t cnt = 0;
-        const HdrStop st = group_walk<G>(arena + si.off, si.len, lane, false, rx_limit<CBC>(slots, cap, si.slot), &cnt,
-                                         [&](uint32_t, const RxHdr &h, uint32_t) { b += h.dlen; });
+        HdrStop st;
+        const uint32_t cnt = rx_count_conn<G, CBC>(si, arena, slots, cap, lane, &st, &b);
         if (q == 0) {
             counts[i] = cnt;
             stops[i] = st;
@@ -427,19 +397,7 @@ __global__ __launch_bounds__(RX_THREADS) void in_emit_group_kernel(const tlsrec_
     const uint32_t i = blockIdx.x * (RX_THREADS / G) + (uint32_t) (tid / G);
     if (i >= n) return;
     const tlsrec_stream_in si = s[i];
-    const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
-    const uint64_t seq0 = be64(si.in_ctr);
-    tlsrec_batch_rec *out = recs + offs[i];
-    const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
-    uint32_t cnt;
-    group_walk<G>(arena + si.off, si.len, lane, tls13, lim, &cnt, [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
-        /* in_ctr + the records before that took a number */
-        const tlsrec_batch_rec d = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
-        if (offs[i] + k < max_records) {                /* (launched before the host has checked the total) */
-            out[k] = d;
-            guard_result(&res[offs[i] + k]);
-        }
-    });
+    rx_emit_conn<G, CBC>(si, arena, slots, cap, lane, offs[i], recs, max_records, res);
 }
 
 /* ---------------- receive, one framing pass (r06, second form) ----------
@@ -531,14 +489,12 @@ __device__ __forceinline__ uint32_t claim_tile(uint32_t *ctr, uint32_t *sh)
     return *sh;
 }
 
-/* Stream receive framing in one pass: RG lanes per connection as
- * in_count_group_kernel / in_emit_group_kernel; a tile is RX_CH chunks of
- * RX_CONNS connections (chunk c's group g takes connection c RX_CONNS + g of
- * the tile), so 1 M records of 4-record streams make 2 K tiles, not 16 K.
- * Writes counts, stops, offs (offs[n] = the batch's record count) and the
- * descriptors (at most max_records of them). */
-/* G lanes per connection (as in_count_group_kernel), CH chunks per tile, NT
- * threads per workgroup */
+/* Stream receive framing in one pass: G lanes per connection as in_count_group_kernel / in_emit_group_kernel
+ * (G = 4 / 8 / 16, never 1), NT threads per workgroup; a tile is CH chunks of NT / G connections (chunk c's
+ * group g takes connection c NT / G + g of the tile) -- PLAN_RX_TILE = 128 connections at every G, by which the
+ * host sizes the grid and the tile status words (stream_rx_plan): one chunk of 128 at 4 lanes, two of 64 at 8,
+ * four of 32 at 16.  Writes counts, stops, offs (offs[n] = the batch's record count) and the descriptors (at
+ * most max_records of them). */
 #ifndef TLSREC_RX_FRAME_NT
 #define TLSREC_RX_FRAME_NT 512
 #endif
@@ -553,6 +509,7 @@ __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s,
 {
     constexpr int RX_CH = CH, RX_CONNS_G = NT / G, RX_TILE = RX_CH * RX_CONNS_G;
     static_assert(RX_TILE <= NT && RX_TILE <= 128 * 2, "tile scan");
+    static_assert(RX_TILE == (int) tlsrec::PLAN_RX_TILE, "the tile the host plans with (tlsrec_plan.h)");
     __shared__ uint32_t sh_tile, sh_cnt[RX_TILE], sh_off[RX_TILE];
     const int tid = threadIdx.x, lane = tid & 63, q = tid & (G - 1), g = tid / G;
     const uint32_t tile = claim_tile(tctr, &sh_tile);
@@ -563,8 +520,8 @@ __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s,
         uint32_t cnt = 0;
         if (i < n) {
             const tlsrec_stream_in si = s[i];
-            const HdrStop st = group_walk<G>(arena + si.off, si.len, lane, false, rx_limit<CBC>(slots, cap, si.slot),
-                                             &cnt, [&](uint32_t, const RxHdr &h, uint32_t) { b += h.dlen; });
+            HdrStop st;
+            cnt = rx_count_conn<G, CBC>(si, arena, slots, cap, lane, &st, &b);
             if (q == 0) {
                 counts[i] = cnt;
                 stops[i] = st;
@@ -607,17 +564,7 @@ __global__ __launch_bounds__(NT) void in_frame_kernel(const tlsrec_stream_in *s,
         const uint32_t cnt = sh_cnt[c * RX_CONNS_G + g], off = sh_off[c * RX_CONNS_G + g];
         if (i >= n || !cnt) continue;                     /* group-uniform */
         const tlsrec_stream_in si = s[i];
-        const bool tls13 = slot_minor<CBC>(slots, cap, si.slot) == 4;
-        const uint64_t seq0 = be64(si.in_ctr);
-        tlsrec_batch_rec *out = recs + off;
-        const uint32_t lim = rx_limit<CBC>(slots, cap, si.slot);
-        uint32_t c2;
-        group_walk<G>(arena + si.off, si.len, lane, tls13, lim, &c2,
-                      [&](uint32_t k, const RxHdr &h, uint32_t ccs_before) {
-            if (off + k >= max_records) return;
-            out[k] = rx_desc(si, tls13, h.pos, h.type, h.v0, h.v1, h.dlen, seq0 + (k - ccs_before));
-            guard_result(&res[off + k]);
-        });
+        rx_emit_conn<G, CBC>(si, arena, slots, cap, lane, off, recs, max_records, res);
     }
 }
 
@@ -1202,10 +1149,45 @@ __global__ void dtls_count_kernel(const tlsrec_dtls_in *c, uint32_t n, const tls
     wave_add_bytes(bytes, b);
 }
 
-/* One descriptor per record.  A record is decrypted when its epoch matches
- * and the window the connection arrived with does not reject it: the window
- * only ever gains records, so every record the in-order pass will accept is
+/* One descriptor per record (rx_desc's counterpart), all but its slot: the record whose header is at buf_off,
+ * ctr its explicit epoch + sequence number (8 bytes, :3683-3687). */
+__device__ __forceinline__ tlsrec_batch_rec dtls_fill(uint64_t buf_off, uint32_t data_offset, uint32_t data_len,
+                                                      uint32_t cid_len, uint8_t type, uint8_t v0, uint8_t v1,
+                                                      const void *ctr)
+{
+    tlsrec_batch_rec r;
+    memset(&r, 0, sizeof(r));
+    r.buf_off = buf_off;                                    /* rec->buf = the header (:3715-3716) */
+    r.buf_len = data_offset + data_len;
+    r.data_offset = data_offset;
+    r.data_len = data_len;
+    memcpy(r.ctr, ctr, 8);
+    r.type = type;
+    r.ver[0] = v0;
+    r.ver[1] = v1;
+    r.cid_len = (uint8_t) cid_len;
+    r.cid_off[0] = 11;                                      /* the CID follows the sequence number */
+    return r;
+}
+
+/* Its slot.  A record is decrypted when its epoch matches and the window the connection arrived with (w0) does
+ * not reject seq48(): the window only ever gains records, so every record the in-order pass will accept is
  * among them (replayed copies of a record that then fails its MAC included). */
+template <typename F>
+__device__ __forceinline__ uint32_t dtls_slot(const tlsrec_dtls_in &ci, const ReplayWindow &w0, uint32_t epoch, F seq48)
+{
+    return (epoch == ci.in_epoch && w0.fresh_s(seq48())) ? ci.slot : NO_SLOT;
+}
+
+/* The descriptor of the record a walk found: h in the datagram at base, p its header bytes */
+__device__ __forceinline__ tlsrec_batch_rec dtls_desc(const tlsrec_dtls_in &ci, const ReplayWindow &w0, uint64_t base,
+                                                      const DtlsHdr &h, const uint8_t *p)
+{
+    tlsrec_batch_rec r = dtls_fill(base + h.pos, h.data_offset, h.data_len, h.cid_len, p[0], p[1], p[2], p + 3);
+    r.slot = dtls_slot(ci, w0, ((uint32_t) p[3] << 8) | p[4], [&] { return ReplayWindow::seq48(p + 3); });
+    return r;
+}
+
 template <bool CBC>
 __global__ void dtls_emit_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsrec_dgram *dg, uint32_t ndg,
                                  const uint8_t *arena, const uint32_t *offs, const SlotState *slots, uint32_t cap,
@@ -1221,22 +1203,8 @@ __global__ void dtls_emit_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsr
     for (uint32_t d = ci.first_dgram; d < ci.first_dgram + ci.ndgram; d++) {
         const uint64_t base = dg[d].off;
         dtls_walk(arena + base, dgram_len(dg[d], maxdg), ci.cid_len, [&](const DtlsHdr &h, const uint8_t *p) {
-            tlsrec_batch_rec r;
-            memset(&r, 0, sizeof(r));
-            r.buf_off = base + h.pos;                  /* rec->buf = the header (:3715-3716) */
-            r.buf_len = h.data_offset + h.data_len;
-            r.data_offset = h.data_offset;
-            r.data_len = h.data_len;
-            memcpy(r.ctr, p + 3, 8);                   /* explicit epoch + sequence number (:3683-3687) */
-            r.type = p[0];
-            r.ver[0] = p[1];
-            r.ver[1] = p[2];
-            r.cid_len = (uint8_t) h.cid_len;
-            r.cid_off[0] = 11;                         /* the CID follows the sequence number */
-            const uint32_t epoch = ((uint32_t) p[3] << 8) | p[4];
-            r.slot = (epoch == ci.in_epoch && w0.fresh(p + 3)) ? ci.slot : NO_SLOT;
             if (k < max_records) {                     /* (launched before the host has checked the total) */
-                recs[k] = r;
+                recs[k] = dtls_desc(ci, w0, base, h, p);
                 guard_result(&res[k]);
             }
             k++;
@@ -1251,7 +1219,11 @@ __global__ void dtls_emit_kernel(const tlsrec_dtls_in *c, uint32_t n, const tlsr
  * fields in LDS (24 B each) and the emit builds those descriptors from there,
  * without a second walk over the header lines (r06; a connection with more
  * records walks again). */
-constexpr int DG_THREADS = 256;
+constexpr int DG_THREADS = tlsrec::PLAN_DG_TILE;
+/* 1: the frame kernel's last tile writes the totals into the host's mailbox (r06); 0 in A/B builds: the totals kernel */
+#ifndef TLSREC_DTLS_LASTTILE_MB
+#define TLSREC_DTLS_LASTTILE_MB 1
+#endif
 template <int S, bool CBC>
 __global__ __launch_bounds__(DG_THREADS) void dtls_frame_kernel(const tlsrec_dtls_in *c, uint32_t n,
                                                                 const tlsrec_dgram *dg, uint32_t ndg,
@@ -1348,23 +1320,13 @@ __global__ __launch_bounds__(DG_THREADS) void dtls_frame_kernel(const tlsrec_dtl
         if (!recs) return;
         for (uint32_t j = 0; j < cnt && off + j < max_records; j++) {
             const uint2 o = st_off[j][tid], cc = st_ctr[j][tid], m = st_meta[j][tid];
-            tlsrec_batch_rec r;
-            memset(&r, 0, sizeof(r));
-            r.buf_off = o.x | (uint64_t) o.y << 32;             /* rec->buf = the header (:3715-3716) */
-            r.data_len = m.x & 0xffffu;
-            r.data_offset = m.x >> 16;
-            r.buf_len = r.data_offset + r.data_len;
-            memcpy(r.ctr, &cc, 8);                              /* explicit epoch + sequence number (:3683-3687) */
-            r.type = (uint8_t) m.y;
-            r.ver[0] = (uint8_t) (m.y >> 8);
-            r.ver[1] = (uint8_t) (m.y >> 16);
-            r.cid_len = (uint8_t) (m.y >> 24);
-            r.cid_off[0] = 11;                                  /* the CID follows the sequence number */
+            tlsrec_batch_rec r = dtls_fill(o.x | (uint64_t) o.y << 32, m.x >> 16, m.x & 0xffffu, m.y >> 24, (uint8_t) m.y,
+                                           (uint8_t) (m.y >> 8), (uint8_t) (m.y >> 16), &cc);
             const uint32_t epoch = (cc.x & 0xffu) << 8 | ((cc.x >> 8) & 0xffu);
             const uint64_t s48 = (uint64_t) ((cc.x >> 16) & 0xffu) << 40 | (uint64_t) (cc.x >> 24) << 32 |
                                  (uint64_t) (cc.y & 0xffu) << 24 | ((cc.y >> 8) & 0xffu) << 16 |
                                  ((cc.y >> 16) & 0xffu) << 8 | (cc.y >> 24);
-            r.slot = (epoch == ci.in_epoch && w0.fresh_s(s48)) ? ci.slot : NO_SLOT;
+            r.slot = dtls_slot(ci, w0, epoch, [&] { return s48; });
             recs[off + j] = r;
             guard_result(&res[off + j]);
         }
@@ -1375,21 +1337,7 @@ __global__ __launch_bounds__(DG_THREADS) void dtls_frame_kernel(const tlsrec_dtl
                          dg_limit<CBC>(slots, cap, ci.slot),
                          [&](uint64_t base, const DtlsHdr &h, const uint8_t *p) {
                              if (recs && k < max_records) {
-                                 tlsrec_batch_rec r;
-                                 memset(&r, 0, sizeof(r));
-                                 r.buf_off = base + h.pos;                  /* rec->buf = the header (:3715-3716) */
-                                 r.buf_len = h.data_offset + h.data_len;
-                                 r.data_offset = h.data_offset;
-                                 r.data_len = h.data_len;
-                                 memcpy(r.ctr, p + 3, 8);                   /* explicit epoch + sequence number (:3683-3687) */
-                                 r.type = p[0];
-                                 r.ver[0] = p[1];
-                                 r.ver[1] = p[2];
-                                 r.cid_len = (uint8_t) h.cid_len;
-                                 r.cid_off[0] = 11;                         /* the CID follows the sequence number */
-                                 const uint32_t epoch = ((uint32_t) p[3] << 8) | p[4];
-                                 r.slot = (epoch == ci.in_epoch && w0.fresh(p + 3)) ? ci.slot : NO_SLOT;
-                                 recs[k] = r;
+                                 recs[k] = dtls_desc(ci, w0, base, h, p);
                                  guard_result(&res[k]);
                              }
                              k++;
@@ -1643,8 +1591,21 @@ using namespace tlsst;
 /* ======================================================================
  * host side
  * ==================================================================== */
+/* This file's environment switches are FrameKnobs (tlsrec_plan.h), read once per call.  The framing plans,
+ * exported for the CPU tests as tlsrec__gcm_plan is (knobs == NULL: the environment): */
+extern "C" void tlsrec__stream_rx_plan(uint32_t n, uint32_t max_records, const FrameKnobs *knobs, StreamRxPlan *out)
+{
+    *out = tlsrec::stream_rx_plan(n, max_records, knobs ? *knobs : tlsrec::frame_knobs_from_env());
+}
+
+extern "C" void tlsrec__dtls_rx_plan(uint32_t nconns, uint32_t ndgrams, const FrameKnobs *knobs, DtlsRxPlan *out)
+{
+    *out = tlsrec::dtls_rx_plan(nconns, ndgrams, knobs ? *knobs : tlsrec::frame_knobs_from_env());
+}
+
 namespace {
 struct Scratch {
+    FrameKnobs knobs;                      /* the call's switches: each call reads them first */
     tlsrec_scratch_lease lease = { nullptr, nullptr };
     uint32_t *counts = nullptr, *offs = nullptr;
     HdrStop *stops = nullptr;
@@ -1654,56 +1615,32 @@ struct Scratch {
     void *scan_tmp = nullptr;
     size_t scan_bytes = 0;
 };
+/* a receive call's scratch, and what tlsrec_stream_decrypt_ex and tlsrec_dtls_decrypt_ex carry from rx_begin to rx_end */
+struct RxCall : Scratch {
+    hipStream_t st = nullptr;
+    const SlotState *slots = nullptr;
+    uint32_t cap = 0, total = 0, avg = 0;   /* total, avg: the framing's record count and mean record size */
+    bool cbc = false;                       /* the CBC kernels (a table without CBC slots: the plain call's) */
+};
 }
 
-/* The environment switches of this file, read on every call (the tests flip
- * them between calls).  All but the last are the default path against an
- * older or alternative one kept for A/B runs and as the tests' second path:
- *   TLSREC_RX_FUSED=0         DTLS receive framing as count, scan and emit
- *                             kernels (r05 / early r06) instead of one pass
- *   TLSREC_RX_FUSED_STREAM=1  stream receive framing in one pass (measured
- *                             slower than its three kernels)
- *   TLSREC_RX_GROUPWALK=0     the r05 stream receive framing: one lane per
- *                             connection in the count and emit kernels
- *   TLSREC_DTLS_STASH=0       the DTLS frame kernel's emit walks the headers
- *                             again instead of reading the count walk's LDS copy
- *   TLSREC_RX_PREFILL=0       the receive batch runs its guard kernel although
- *                             the emit kernels wrote the guard results
- *   TLSREC_RX_MAILBOX=0       the totals come back by two copies and a stream
- *                             synchronize (before r06's second session)
- *   TLSREC_STREAM_SRC=0       the send paths copy the application data into
- *                             the output stream first (r04) instead of reading
- *                             it in place (r05)
- *   TLSREC_RX_RG=4|8|16       forces rx_group()'s lanes per connection */
-static bool env_flag(const char *name, bool dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) != 0 : dflt;
-}
-static int env_int(const char *name)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
-}
-
-/* lanes per connection of the receive header walk: the records a
- * connection can hold on average by the caller's capacity (max_records /
- * connections) -- 4, 8 or 16; TLSREC_RX_RG forces one */
-static int rx_group(uint32_t n, uint32_t max_records)
-{
-    const int g = env_int("TLSREC_RX_RG");
-    if (g == 4 || g == 8 || g == 16) return g;
-    const uint64_t per = n ? ((uint64_t) max_records + n - 1) / n : 16;
-    return per <= 4 ? 4 : (per <= 8 ? 8 : 16);
-}
-
-/* f(std::integral_constant<int, g>) for the lane-group kernels' template argument */
+/* f(std::integral_constant<int, g>) for the count / emit kernels' template argument (StreamRxPlan::G) */
 template <typename F>
 static void with_rx_group(int g, F f)
 {
-    if (g == 4) f(std::integral_constant<int, 4>{});
+    if (g == 1) f(std::integral_constant<int, 1>{});
+    else if (g == 4) f(std::integral_constant<int, 4>{});
     else if (g == 8) f(std::integral_constant<int, 8>{});
     else f(std::integral_constant<int, 16>{});
+}
+
+/* f(std::integral_constant<int, s>) for dtls_frame_kernel's stash depth (DtlsRxPlan::S) */
+template <typename F>
+static void with_stash(int s, F f)
+{
+    if (s == 4) f(std::integral_constant<int, 4>{});
+    else if (s == 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 0>{});
 }
 
 /* tiles: the one-pass framing kernels' tile status words (0 = none) */
@@ -1740,10 +1677,10 @@ thread_local Mailbox t_mbox;
 
 /* the calling thread's mailbox (device pointer) and the next sequence
  * number; null with the copy path (TLSREC_RX_MAILBOX=0) or no mailbox */
-static TotMbox *mailbox_next(uint64_t *seq)
+static TotMbox *mailbox_next(const FrameKnobs &knobs, uint64_t *seq)
 {
     *seq = 0;
-    if (!env_flag("TLSREC_RX_MAILBOX", true)) return nullptr;
+    if (!knobs.mailbox) return nullptr;
     Mailbox &m = t_mbox;
     if (!m.h) {
         void *h = nullptr, *d = nullptr;
@@ -1765,7 +1702,7 @@ static TotMbox *mailbox_next(uint64_t *seq)
  * *seq = the value collect_totals waits for (0: the copy path, nothing queued) */
 static int publish_totals(Scratch &sc, uint32_t n, hipStream_t st, uint64_t *seq)
 {
-    TotMbox *mb = mailbox_next(seq);
+    TotMbox *mb = mailbox_next(sc.knobs, seq);
     if (!mb) {
         *seq = 0;
         return 0;
@@ -1858,97 +1795,94 @@ static void with_cbc(bool cbc, F f)
     else f(std::false_type{});
 }
 
+/* Before the framing: the options, the arguments (args_ok: the call's own pointer check), the switches, the key table */
+static int rx_begin(RxCall &c, const tlsrec_keytab *kt, const tlsrec_frame_opts *opts, bool args_ok, void *stream,
+                    uint32_t *nrecords)
+{
+    if (nrecords) *nrecords = 0;
+    if (const int orc = frame_opts(opts, false, &c.cbc)) return orc;
+    c.cbc = c.cbc && tlsrec__keytab_has_cbc(kt);
+    if (!kt || !args_ok) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    c.knobs = tlsrec::frame_knobs_from_env();
+    c.st = (hipStream_t) stream;
+    c.slots = tlsrec__keytab_slots(kt);
+    c.cap = tlsrec_keytab_capacity(kt);
+    return 0;
+}
+
+/* After the framing (r: its status): the totals against the caller's capacity and arrays (have_out: every per-record
+ * array the call needs), the batch in place, the call's finish kernel (finish() launches it), release */
+template <typename F>
+static int rx_end(RxCall &c, int r, const tlsrec_keytab *kt, uint8_t *arena, tlsrec_batch_rec *recs,
+                  tlsrec_batch_res *res, bool have_out, uint32_t max_records, void *stream, uint32_t *nrecords, F finish)
+{
+    if (r == 0 && c.total > max_records) r = TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
+    if (r == 0 && c.total && !have_out) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (r == 0 && c.total)
+        r = tlsrec__batch_sized(kt, recs, res, c.total, arena, arena, stream, 1, c.avg, c.knobs.prefill, c.cbc);
+    if (r == 0) {
+        finish();
+        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    }
+    tlsrec__scratch_release(&c.lease);
+    if (r == 0 && nrecords) *nrecords = c.total;
+    return r;
+}
+
 extern "C" int tlsrec_stream_decrypt_ex(const tlsrec_keytab *kt, const tlsrec_stream_in *streams, uint32_t nstreams,
                                         uint8_t *arena, tlsrec_batch_rec *recs, tlsrec_batch_res *res,
                                         uint32_t max_records, tlsrec_stream_in_res *sres, uint32_t *nrecords,
                                         void *stream, const tlsrec_frame_opts *opts)
 {
-    if (nrecords) *nrecords = 0;
-    bool cbc;
-    if (const int orc = frame_opts(opts, false, &cbc)) return orc;
-    cbc = cbc && tlsrec__keytab_has_cbc(kt);      /* (a table without CBC slots: the plain call's kernels) */
-    if (!kt || (nstreams && (!streams || !arena || !sres))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (nstreams == 0) return 0;
-    hipStream_t st = (hipStream_t) stream;
-    const SlotState *slots = tlsrec__keytab_slots(kt);
-    const uint32_t cap = tlsrec_keytab_capacity(kt);
-    Scratch sc;
-    const bool gw = env_flag("TLSREC_RX_GROUPWALK", true);
-    const bool fused = env_flag("TLSREC_RX_FUSED_STREAM", false) && gw;
-    /* one pass: G lanes per connection, tiles of 512 connections (G = 4:
-     * two chunks of 128) or 128 (G = 16: eight chunks of 16) */
-    const int rg = rx_group(nstreams, max_records);
-    const uint32_t ftile = rg == 4 ? 2u * 64u : (rg == 8 ? 4u * 32u : 8u * 16u);
-    const uint32_t tiles = blocks(nstreams, ftile);
-    int r = scratch_alloc(sc, nstreams, st, fused ? tiles : 0u);
-    uint32_t total = 0, avg = 0;
+    RxCall c;
+    int r = rx_begin(c, kt, opts, !nstreams || (streams && arena && sres), stream, nrecords);
+    if (r || nstreams == 0) return r;
     const uint8_t *ar = arena;
-    TLSREC_LAUNCH_LOG(TLSREC_LOG_STREAM_RX_FRAME, fused, gw ? rg : 1, 0, 0);
-    if (r == 0 && fused) {
+    const StreamRxPlan p = tlsrec::stream_rx_plan(nstreams, max_records, c.knobs);
+    r = scratch_alloc(c, nstreams, c.st, p.fused ? p.tiles : 0u);
+    TLSREC_LAUNCH_LOG(TLSREC_LOG_STREAM_RX_FRAME, p.fused, p.G, 0, 0);
+    if (r == 0 && p.fused) {
         /* count, scan and emit in one pass (descriptors up to max_records) */
-        /* tiles of 128 connections: one chunk of 128 at 4 lanes (512 threads),
-         * or chunks of 64 / 32 at 8 / 16 lanes */
-        with_rx_group(rg, [&](auto G) {
-            with_cbc(cbc, [&](auto C) {
-                constexpr int FNT = TLSREC_RX_FRAME_NT;
-                hipLaunchKernelGGL((in_frame_kernel<G(), (G() * 128) / FNT, FNT, C()>), dim3(tiles), dim3(FNT), 0, st,
-                                   streams, nstreams, ar, slots, cap, sc.counts, sc.offs, sc.stops, sc.bytes, sc.tstat,
-                                   sc.tctr, recs, (recs && res) ? max_records : 0u, res);
+        with_rx_group(p.G, [&](auto G) {
+            with_cbc(c.cbc, [&](auto C) {
+                constexpr int FNT = TLSREC_RX_FRAME_NT, LANES = decltype(G)::value;
+                if constexpr (LANES != 1)          /* (the plan: one pass only with the group walk) */
+                    hipLaunchKernelGGL((in_frame_kernel<LANES, LANES * (int) tlsrec::PLAN_RX_TILE / FNT, FNT, C()>),
+                                       dim3(p.tiles), dim3(FNT), 0, c.st, streams, nstreams, ar, c.slots, c.cap,
+                                       c.counts, c.offs, c.stops, c.bytes, c.tstat, c.tctr, recs,
+                                       (recs && res) ? max_records : 0u, res);
             });
         });
-        r = hipGetLastError() == hipSuccess ? fetch_total(sc, nstreams, st, &total, &avg)
+        r = hipGetLastError() == hipSuccess ? fetch_total(c, nstreams, c.st, &c.total, &c.avg)
                                             : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
     } else if (r == 0) {
-        if (gw)
-            with_rx_group(rg, [&](auto G) {
-                with_cbc(cbc, [&](auto C) {
-                    hipLaunchKernelGGL((in_count_group_kernel<G(), C()>), dim3(blocks(nstreams + 1, RX_THREADS / G())),
-                                       dim3(RX_THREADS), 0, st, streams, nstreams, ar, slots, cap, sc.counts, sc.stops,
-                                       sc.bytes);
-                });
+        with_rx_group(p.G, [&](auto G) {
+            with_cbc(c.cbc, [&](auto C) {
+                hipLaunchKernelGGL((in_count_group_kernel<G(), C()>), dim3(p.count_grid), dim3(RX_THREADS), 0, c.st,
+                                   streams, nstreams, ar, c.slots, c.cap, c.counts, c.stops, c.bytes);
             });
-        else
-            with_cbc(cbc, [&](auto C) {
-                hipLaunchKernelGGL(in_count_kernel<C()>, dim3(blocks(nstreams + 1, 256)), dim3(256), 0, st, streams,
-                                   nstreams, ar, slots, cap, sc.counts, sc.stops, sc.bytes);
-            });
+        });
         uint64_t seq = 0;
-        r = hipGetLastError() == hipSuccess ? scan_publish(sc, nstreams, st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+        r = hipGetLastError() == hipSuccess ? scan_publish(c, nstreams, c.st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         /* the descriptors are emitted while the host collects the totals
          * (r06; at most max_records of them: the check follows) */
         if (r == 0 && recs && res) {
-            if (gw)
-                with_rx_group(rg, [&](auto G) {
-                    with_cbc(cbc, [&](auto C) {
-                        hipLaunchKernelGGL((in_emit_group_kernel<G(), C()>), dim3(blocks(nstreams, RX_THREADS / G())),
-                                           dim3(RX_THREADS), 0, st, streams, nstreams, ar, sc.offs, slots, cap, recs,
-                                           max_records, res);
-                    });
+            with_rx_group(p.G, [&](auto G) {
+                with_cbc(c.cbc, [&](auto C) {
+                    hipLaunchKernelGGL((in_emit_group_kernel<G(), C()>), dim3(p.emit_grid), dim3(RX_THREADS), 0, c.st,
+                                       streams, nstreams, ar, c.offs, c.slots, c.cap, recs, max_records, res);
                 });
-            else
-                with_cbc(cbc, [&](auto C) {
-                    hipLaunchKernelGGL(in_emit_kernel<C()>, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams,
-                                       nstreams, ar, sc.offs, slots, cap, recs, max_records, res);
-                });
+            });
             if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         }
-        if (r == 0) r = collect_totals(sc, nstreams, st, seq, &total, &avg);
+        if (r == 0) r = collect_totals(c, nstreams, c.st, seq, &c.total, &c.avg);
     }
-    if (r == 0 && total > max_records) r = TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
-    if (r == 0 && total && (!recs || !res)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (r == 0 && total)
-        r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg,
-                                env_flag("TLSREC_RX_PREFILL", true), cbc);
-    if (r == 0) {
-        with_cbc(cbc, [&](auto C) {
-            hipLaunchKernelGGL(in_finish_kernel<C()>, dim3(blocks(nstreams, 256)), dim3(256), 0, st, streams, nstreams,
-                               sc.offs, sc.counts, sc.stops, slots, cap, recs, res, sres);
+    return rx_end(c, r, kt, arena, recs, res, recs && res, max_records, stream, nrecords, [&] {
+        with_cbc(c.cbc, [&](auto C) {
+            hipLaunchKernelGGL(in_finish_kernel<C()>, dim3(blocks(nstreams, 256)), dim3(256), 0, c.st, streams, nstreams,
+                               c.offs, c.counts, c.stops, c.slots, c.cap, recs, res, sres);
         });
-        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
-    tlsrec__scratch_release(&sc.lease);
-    if (r == 0 && nrecords) *nrecords = total;
-    return r;
+    });
 }
 
 extern "C" int tlsrec_stream_decrypt(const tlsrec_keytab *kt, const tlsrec_stream_in *streams, uint32_t nstreams,
@@ -2032,6 +1966,7 @@ static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, 
     const SlotState *slots = tlsrec__keytab_slots(kt);
     const uint32_t cap = tlsrec_keytab_capacity(kt);
     Scratch sc;
+    sc.knobs = tlsrec::frame_knobs_from_env();
     int r = scratch_alloc(sc, nstreams, st);
     uint32_t total = 0, avg = 0;
     if (r == 0) {
@@ -2050,7 +1985,7 @@ static int send_impl(const tlsrec_keytab *kt, const tlsrec_stream_out *streams, 
          * holds a CBC slot: copy, then in place */
         uint64_t *srcoff = nullptr;
         tlsrec_scratch_lease sl = { nullptr, nullptr };
-        if (tlsrec__keytab_src_ok(kt) && env_flag("TLSREC_STREAM_SRC", true) &&
+        if (tlsrec__keytab_src_ok(kt) && sc.knobs.stream_src &&
             tlsrec__scratch_acquire(st, 3, (size_t) total * sizeof(uint64_t), &sl) == 0)
             srcoff = (uint64_t *) sl.mem;
         TLSREC_LAUNCH_LOG(TLSREC_LOG_SEND_FRAME, srcoff != nullptr, W::LOG_P1, 0, 0);
@@ -2138,87 +2073,60 @@ extern "C" int tlsrec_dtls_decrypt_ex(const tlsrec_keytab *kt, const tlsrec_dtls
                                       uint32_t max_records, tlsrec_dtls_in_res *cres, uint32_t *nrecords, void *stream,
                                       const tlsrec_frame_opts *opts)
 {
-    if (nrecords) *nrecords = 0;
-    bool cbc;
-    if (const int orc = frame_opts(opts, false, &cbc)) return orc;
-    cbc = cbc && tlsrec__keytab_has_cbc(kt);      /* (a table without CBC slots: the plain call's kernels) */
-    if (!kt || (nconns && (!conns || !cres || (ndgrams && (!dgrams || !arena))))) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (nconns == 0) return 0;
-    hipStream_t st = (hipStream_t) stream;
-    const SlotState *slots = tlsrec__keytab_slots(kt);
-    const uint32_t cap = tlsrec_keytab_capacity(kt);
-    Scratch sc;
-    const bool fused = env_flag("TLSREC_RX_FUSED", true);
-    const uint32_t tiles = blocks(nconns, DG_THREADS);
-    int r = scratch_alloc(sc, nconns, st, fused ? tiles : 0u);
-    uint32_t total = 0, avg = 0;
+    RxCall c;
+    int r = rx_begin(c, kt, opts, !nconns || (conns && cres && (!ndgrams || (dgrams && arena))), stream, nrecords);
+    if (r || nconns == 0) return r;
+    const uint8_t *ar = arena;
+    const DtlsRxPlan p = tlsrec::dtls_rx_plan(nconns, ndgrams, c.knobs);
+    r = scratch_alloc(c, nconns, c.st, p.fused ? p.tiles : 0u);
     tlsrec_scratch_lease dgl = { nullptr, nullptr };
     uint32_t *dgst = nullptr;
-    if (r == 0 && fused) {
-        /* count, scan and emit in one pass (descriptors up to max_records) */
-        uint64_t seq = 0;
-#ifndef TLSREC_DTLS_LASTTILE_MB
-#define TLSREC_DTLS_LASTTILE_MB 1
-#endif
-        /* the frame kernel's last tile writes the totals into the mailbox
-         * (r06; 0 in A/B builds: the totals kernel after the frame kernel) */
-        TotMbox *mb = TLSREC_DTLS_LASTTILE_MB ? mailbox_next(&seq) : nullptr;
+    uint64_t seq = 0;
+    if (r == 0) TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, p.S, 0, 0, 0);
+    if (r == 0 && p.fused) {
+        /* count, scan and emit in one pass (descriptors up to max_records);
+         * its last tile writes the totals into the mailbox (r06) */
+        TotMbox *mb = TLSREC_DTLS_LASTTILE_MB ? mailbox_next(c.knobs, &seq) : nullptr;
         /* the datagram summaries for the finish (none: it walks the headers) */
-        if (ndgrams && tlsrec__scratch_acquire(st, 2, (size_t) ndgrams * 4, &dgl) == 0) dgst = (uint32_t *) dgl.mem;
-        /* LDS for the records of a connection of mean size (4 / 16 records:
-         * 24 / 96 KiB per workgroup); TLSREC_DTLS_STASH=0: the emit walks the
-         * headers again */
-        const uint32_t per = nconns ? (uint32_t) ((ndgrams + nconns - 1) / nconns) : 0;
-#define TLSREC_DTLS_FRAME(S_) do { TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, S_, 0, 0, 0); \
-                           with_cbc(cbc, [&](auto C) { \
-                           hipLaunchKernelGGL((dtls_frame_kernel<S_, C()>), dim3(tiles), dim3(DG_THREADS), 0, st, conns, \
-                           nconns, dgrams, ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.offs, sc.bytes, \
-                           sc.tstat, sc.tctr, recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst); }); } while (0)
-        if (!env_flag("TLSREC_DTLS_STASH", true) || per > 16) TLSREC_DTLS_FRAME(0);
-        else if (per > 4) TLSREC_DTLS_FRAME(16);
-        else TLSREC_DTLS_FRAME(4);
-#undef TLSREC_DTLS_FRAME
-        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-        else if (mb) r = collect_totals(sc, nconns, st, seq, &total, &avg);
-        else r = fetch_total(sc, nconns, st, &total, &avg);
-    } else if (r == 0) {
-        TLSREC_LAUNCH_LOG(TLSREC_LOG_DTLS_RX_FRAME, -1, 0, 0, 0);
-        with_cbc(cbc, [&](auto C) {
-            hipLaunchKernelGGL(dtls_count_kernel<C()>, dim3(blocks(nconns + 1, 256)), dim3(256), 0, st, conns, nconns,
-                               dgrams, ndgrams, (const uint8_t *) arena, slots, cap, sc.counts, sc.bytes);
+        if (ndgrams && tlsrec__scratch_acquire(c.st, 2, (size_t) ndgrams * 4, &dgl) == 0) dgst = (uint32_t *) dgl.mem;
+        with_stash(p.S, [&](auto S) {
+            with_cbc(c.cbc, [&](auto C) {
+                hipLaunchKernelGGL((dtls_frame_kernel<S(), C()>), dim3(p.tiles), dim3(DG_THREADS), 0, c.st, conns, nconns,
+                                   dgrams, ndgrams, ar, c.slots, c.cap, c.counts, c.offs, c.bytes, c.tstat, c.tctr,
+                                   recs, (recs && res) ? max_records : 0u, res, mb, seq, dgst);
+            });
         });
-        uint64_t seq = 0;
-        r = hipGetLastError() == hipSuccess ? scan_publish(sc, nconns, st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+        else if (mb) r = collect_totals(c, nconns, c.st, seq, &c.total, &c.avg);
+        else r = fetch_total(c, nconns, c.st, &c.total, &c.avg);
+    } else if (r == 0) {
+        with_cbc(c.cbc, [&](auto C) {
+            hipLaunchKernelGGL(dtls_count_kernel<C()>, dim3(blocks(nconns + 1, 256)), dim3(256), 0, c.st, conns, nconns,
+                               dgrams, ndgrams, ar, c.slots, c.cap, c.counts, c.bytes);
+        });
+        r = hipGetLastError() == hipSuccess ? scan_publish(c, nconns, c.st, &seq) : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         if (r == 0 && recs && res) {   /* emitted while the host collects the totals (as the stream path) */
-            with_cbc(cbc, [&](auto C) {
-                hipLaunchKernelGGL(dtls_emit_kernel<C()>, dim3(blocks(nconns, 256)), dim3(256), 0, st, conns, nconns,
-                                   dgrams, ndgrams, (const uint8_t *) arena, sc.offs, slots, cap, recs, max_records, res);
+            with_cbc(c.cbc, [&](auto C) {
+                hipLaunchKernelGGL(dtls_emit_kernel<C()>, dim3(blocks(nconns, 256)), dim3(256), 0, c.st, conns, nconns,
+                                   dgrams, ndgrams, ar, c.offs, c.slots, c.cap, recs, max_records, res);
             });
             if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
         }
-        if (r == 0) r = collect_totals(sc, nconns, st, seq, &total, &avg);
+        if (r == 0) r = collect_totals(c, nconns, c.st, seq, &c.total, &c.avg);
     }
-    if (r == 0 && total > max_records) r = TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
-    if (r == 0 && total && (!recs || !res || !disp)) r = TLSREC_ERR_SSL_BAD_INPUT_DATA;
-    if (r == 0 && total)
-        r = tlsrec__batch_sized(kt, recs, res, total, arena, arena, stream, 1, avg,
-                                env_flag("TLSREC_RX_PREFILL", true), cbc);
-    if (r == 0) {
-        with_cbc(cbc, [&](auto C) {
-            if (fused)
-                hipLaunchKernelGGL((dtls_finish_kernel<true, C()>), dim3(blocks(nconns, 256)), dim3(256), 0, st, conns,
-                                   nconns, dgrams, ndgrams, arena, sc.offs, sc.counts, slots, cap, recs, res, disp, cres,
-                                   dgst);
+    r = rx_end(c, r, kt, arena, recs, res, recs && res && disp, max_records, stream, nrecords, [&] {
+        with_cbc(c.cbc, [&](auto C) {
+            if (p.fused)
+                hipLaunchKernelGGL((dtls_finish_kernel<true, C()>), dim3(blocks(nconns, 256)), dim3(256), 0, c.st, conns,
+                                   nconns, dgrams, ndgrams, arena, c.offs, c.counts, c.slots, c.cap, recs, res, disp,
+                                   cres, dgst);
             else
-                hipLaunchKernelGGL((dtls_finish_kernel<false, C()>), dim3(blocks(nconns, 256)), dim3(256), 0, st, conns,
-                                   nconns, dgrams, ndgrams, arena, sc.offs, sc.counts, slots, cap, recs, res, disp, cres,
-                                   (const uint32_t *) nullptr);
+                hipLaunchKernelGGL((dtls_finish_kernel<false, C()>), dim3(blocks(nconns, 256)), dim3(256), 0, c.st, conns,
+                                   nconns, dgrams, ndgrams, arena, c.offs, c.counts, c.slots, c.cap, recs, res, disp,
+                                   cres, (const uint32_t *) nullptr);
         });
-        if (hipGetLastError() != hipSuccess) r = TLSREC_ERR_SSL_HW_ACCEL_FAILED;
-    }
+    });
     if (dgl.mem) tlsrec__scratch_release(&dgl);
-    tlsrec__scratch_release(&sc.lease);
-    if (r == 0 && nrecords) *nrecords = total;
     return r;
 }
 

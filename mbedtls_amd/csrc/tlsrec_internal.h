@@ -276,7 +276,7 @@ hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream
  *   DTLS_RX_FRAME   p0 the stash depth S of dtls_frame_kernel (4 / 16 / 0),
  *                   -1 = count, scan and emit kernels
  *   STREAM_RX_FRAME p0 1 = one pass, 0 = three kernels; p1 lanes per
- *                   connection G (1 = the one-lane walks) */
+ *                   connection G (1 = TLSREC_RX_GROUPWALK=0, the kernels at G = 1) */
 enum {
     TLSREC_LOG_GCM = 1,
     TLSREC_LOG_CHACHA = 2,

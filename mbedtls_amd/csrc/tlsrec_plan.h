@@ -8,6 +8,8 @@
  * compiler can build and sweep them alone (tests/c/plan_sweep.cpp), and
  * tests/test_gcm_plan_cpu.py holds them to tests/golden/gcm_plan.json, the
  * shapes recorded on the device before the rule moved here.
+ * stream_rx_plan() and dtls_rx_plan() do the same for stream.hip's receive
+ * framing from the TLSREC_RX_* switches (tests/test_frame_plan_cpu.py).
  */
 #ifndef TLSREC_PLAN_H
 #define TLSREC_PLAN_H
@@ -304,6 +306,67 @@ static inline ChachaPlan chacha_plan(uint32_t n, uint32_t cu, uint32_t lanes_in,
     p.rpw = pick_rpw(n, PLAN_CP_WAVES, 64u / (uint32_t) p.L, cu * 4);
     p.grid = plan_grid(n, PLAN_CP_WAVES, p.rpw);
     return p;
+}
+
+/* ---- receive framing (stream.hip) -------------------------------------- */
+constexpr uint32_t PLAN_RX_THREADS = 256;   /* RX_THREADS: a stream count / emit workgroup, 256 / G connections */
+constexpr uint32_t PLAN_RX_TILE = 128;      /* connections of a one-pass stream tile, at every G (in_frame_kernel) */
+constexpr uint32_t PLAN_DG_TILE = 256;      /* DG_THREADS: connections of a DTLS tile, one lane each */
+
+/* The switches of the stream / DTLS layers and their values in an empty environment: the default path against a
+ * second one kept for A/B runs and tests.  32-bit fields only: mbedtls_amd/_abi.py mirrors the layout. */
+struct FrameKnobs {
+    uint32_t groupwalk = 1;      /* TLSREC_RX_GROUPWALK=0: one lane per connection (G = 1), never one pass */
+    uint32_t fused_stream = 0;   /* TLSREC_RX_FUSED_STREAM=1: stream receive framing in one pass */
+    int32_t rg = 0;              /* TLSREC_RX_RG=4|8|16: forces the lanes per connection; anything else = the rule */
+    uint32_t fused = 1;          /* TLSREC_RX_FUSED=0: DTLS receive framing as count, scan and emit kernels */
+    uint32_t stash = 1;          /* TLSREC_DTLS_STASH=0: the DTLS one pass without its LDS header copy */
+    uint32_t prefill = 1;        /* TLSREC_RX_PREFILL=0: the receive batch runs its guard kernel */
+    uint32_t mailbox = 1;        /* TLSREC_RX_MAILBOX=0: the totals by copies and a stream synchronize */
+    uint32_t stream_src = 1;     /* TLSREC_STREAM_SRC=0: the send paths copy the application data first */
+};
+
+static inline FrameKnobs frame_knobs_from_env(void)   /* once per call: the tests flip the switches between calls */
+{
+    return { plan_env("TLSREC_RX_GROUPWALK", 1) != 0, plan_env("TLSREC_RX_FUSED_STREAM", 0) != 0,
+             plan_env("TLSREC_RX_RG", 0), plan_env("TLSREC_RX_FUSED", 1) != 0, plan_env("TLSREC_DTLS_STASH", 1) != 0,
+             plan_env("TLSREC_RX_PREFILL", 1) != 0, plan_env("TLSREC_RX_MAILBOX", 1) != 0,
+             plan_env("TLSREC_STREAM_SRC", 1) != 0 };
+}
+
+static inline uint32_t plan_blocks(uint64_t n, uint32_t per) { return (uint32_t) ((n + per - 1) / per); }
+
+struct StreamRxPlan {
+    uint32_t fused;        /* count, scan and emit in one pass (the launch log's p0) */
+    int32_t G;             /* lanes per connection: 1 / 4 / 8 / 16 (the launch log's p1) */
+    uint32_t tile, tiles;             /* one pass: connections per tile, and the tiles = its grid */
+    uint32_t count_grid, emit_grid;   /* else: workgroups of 256 / G connections over nstreams + 1 (sentinel), nstreams */
+};
+
+/* Stream receive.  Lanes per connection: the records a connection holds on average by the caller's capacity
+ * (max_records / connections) -- 4, 8 or 16 (r06: a 4-record stream left 12 of 16 lanes idle) */
+static inline StreamRxPlan stream_rx_plan(uint32_t nstreams, uint32_t max_records, const FrameKnobs &k)
+{
+    const uint64_t per = nstreams ? ((uint64_t) max_records + nstreams - 1) / nstreams : 16;
+    const int32_t g = !k.groupwalk ? 1 : (k.rg == 4 || k.rg == 8 || k.rg == 16) ? k.rg : per <= 4 ? 4 : (per <= 8 ? 8 : 16);
+    const uint32_t conns = PLAN_RX_THREADS / (uint32_t) g;
+    return { k.fused_stream && k.groupwalk, g, PLAN_RX_TILE, plan_blocks(nstreams, PLAN_RX_TILE),
+             plan_blocks((uint64_t) nstreams + 1, conns), plan_blocks(nstreams, conns) };
+}
+
+struct DtlsRxPlan {
+    uint32_t fused;   /* count, scan and emit in one pass */
+    int32_t S;        /* its LDS stash depth: 4 / 16 / 0 records per connection; -1 = three kernels (the log's p0) */
+    uint32_t tiles;   /* tiles of PLAN_DG_TILE connections = the one pass's grid */
+};
+
+/* DTLS receive.  The one pass keeps LDS for a mean connection's records (4 / 16: 24 / 96 KiB per workgroup);
+ * beyond 16 datagrams per connection, or with TLSREC_DTLS_STASH=0, its emit walks the headers again. */
+static inline DtlsRxPlan dtls_rx_plan(uint32_t nconns, uint32_t ndgrams, const FrameKnobs &k)
+{
+    const uint64_t per = nconns ? ((uint64_t) ndgrams + nconns - 1) / nconns : 0;
+    const int32_t s = !k.fused ? -1 : (!k.stash || per > 16) ? 0 : (per > 4 ? 16 : 4);
+    return { k.fused != 0, s, plan_blocks(nconns, PLAN_DG_TILE) };
 }
 
 } /* namespace tlsrec */

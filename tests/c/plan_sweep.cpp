@@ -3,8 +3,9 @@
  * over record counts, key counts, size hints, CU counts and lane requests far
  * outside what a device run can reach, under -fsanitize=address,undefined
  * (tests/c/Makefile plan_sweep): no division by zero or overflow, a lane count
- * the kernels have, a grid that covers the batch.  Host only: no library, no
- * device.  Exit status 0 = every plan held.
+ * the kernels have, a grid that covers the batch; and stream_rx_plan() /
+ * dtls_rx_plan() over connection, record and datagram counts up to 2^32 - 1.
+ * Host only: no library, no device.  Exit status 0 = every plan held.
  */
 #include <stdio.h>
 
@@ -89,6 +90,40 @@ int main(void)
         const uint32_t l = gcm_pair_small_l(rpk);
         CHECK(l == 2 || l == 4 || l == 8, "pair_small_l(%u)=%u", rpk, l);
     }
+    /* the receive framing plans: every switch value, counts up to 2^32 - 1 */
+    static const uint32_t cs[] = { 0, 1, 2, 127, 128, 129, 255, 256, 257, 1u << 16, 0x7fffffffu, 0xffffffffu };
+    static const int32_t rgs[] = { 0, 1, 4, 5, 8, 16, -1, 0x7fffffff };
+    for (uint32_t n : cs)
+        for (uint32_t m : cs)
+            for (uint32_t sw = 0; sw < 16; sw++)
+                for (int32_t rg : rgs) {
+                    FrameKnobs k;
+                    k.groupwalk = sw & 1;
+                    k.fused_stream = (sw >> 1) & 1;
+                    k.fused = (sw >> 2) & 1;
+                    k.stash = (sw >> 3) & 1;
+                    k.rg = rg;
+                    const StreamRxPlan p = stream_rx_plan(n, m, k);
+                    CHECK(p.G == 1 || p.G == 4 || p.G == 8 || p.G == 16, "G=%d", p.G);
+                    if (p.G != 1 && p.G != 4 && p.G != 8 && p.G != 16) continue;
+                    CHECK((p.G == 1) == !k.groupwalk && !(p.fused && p.G == 1), "G=%d fused=%u", p.G, p.fused);
+                    const uint64_t conns = PLAN_RX_THREADS / (uint32_t) p.G;
+                    CHECK(p.tile == PLAN_RX_TILE && (uint64_t) p.tiles * p.tile >= n &&
+                              (n == 0 ? p.tiles == 0 : (uint64_t) (p.tiles - 1) * p.tile < n),
+                          "tiles=%u n=%u", p.tiles, n);
+                    CHECK(p.emit_grid * conns >= n && (n == 0 ? p.emit_grid == 0 : (p.emit_grid - 1) * conns < n),
+                          "emit_grid=%u n=%u G=%d", p.emit_grid, n, p.G);
+                    CHECK(p.count_grid >= 1 && p.count_grid * conns >= (uint64_t) n + 1 &&
+                              (p.count_grid - 1) * conns < (uint64_t) n + 1,
+                          "count_grid=%u n=%u G=%d", p.count_grid, n, p.G);
+                    const DtlsRxPlan d = dtls_rx_plan(n, m, k);
+                    CHECK(d.fused == k.fused && (d.fused ? (d.S == 0 || d.S == 4 || d.S == 16) : d.S == -1) &&
+                              (k.stash || d.S <= 0),
+                          "S=%d fused=%u stash=%u", d.S, d.fused, k.stash);
+                    CHECK((uint64_t) d.tiles * PLAN_DG_TILE >= n && (n == 0 ? d.tiles == 0 : (uint64_t) (d.tiles - 1) * PLAN_DG_TILE < n),
+                          "dtls tiles=%u n=%u", d.tiles, n);
+                    plans += 2;
+                }
     printf("plan_sweep: %ld plans, %d failed\n", plans, fails);
     return fails ? 1 : 0;
 }

@@ -2,6 +2,7 @@
 against the oracle's restatement of the ssl_get_next_record /
 mbedtls_ssl_write_record loops: byte-exact record streams, per-connection
 status / consumed / sequence numbers, and every stop condition."""
+import functools
 import json
 import os
 
@@ -15,9 +16,11 @@ if not torch.cuda.is_available():  # pragma: no cover
     pytest.skip("needs a GPU", allow_module_level=True)
 
 import mbedtls_amd as M  # noqa: E402
+from mbedtls_amd import _abi  # noqa: E402
 from mbedtls_amd import stream as S  # noqa: E402
 import oracle as O  # noqa: E402
 from tests import batchlib as B  # noqa: E402
+from tests.batchlib import launch_log  # noqa: E402,F401  (fixture)
 from tests.prng import prng_bytes  # noqa: E402
 
 KATS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_kats.json")))
@@ -149,6 +152,128 @@ def test_irregular_record_lengths_match_oracle(fr, monkeypatch):
             assert int(recs[f + k]["buf_off"]) == offs[i] + off
             s0 = offs[i] + off + doff
             assert a[s0:s0 + dlen].tobytes() == wbuf[off + doff:off + doff + dlen], (i, k)
+    c.close()
+
+
+MIX_N = 515                                     # two full G = 1 workgroups and a partial one; five one-pass tiles
+MIX_COUNTS = [0, 1, 2, 3, 4, 5, 15, 16, 17, 33]
+CCS = bytes([20, 3, 3, 0, 1, 1])
+NO_SLOT = 0xFFFFFFFF
+# connection -> what follows its three good records
+MIX_BAD = {37: "type-first", 141: "type-later", 262: "short-header", 391: "short-body", 502: "too-long"}
+
+
+def _split(wire):
+    out, pos = [], 0
+    while pos < len(wire):
+        n = 5 + int.from_bytes(wire[pos + 3:pos + 5], "big")
+        out.append(wire[pos:pos + n])
+        pos += n
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _walk_mix():
+    """(slots, conns, framed, want): MIX_N connections of 0..33 records with
+    contents of 1..40 bytes -- per ten connections every count of MIX_COUNTS,
+    ten with records of one length (group rounds of G) then ten with
+    consecutive lengths that differ (rounds of 1), the four slots in turn;
+    the TLS 1.3 slots' connections with a CCS as first, a middle or the last
+    record in turn; the MIX_BAD connections stop at a header.  framed[i]: the
+    records the header walk frames, (position, type, sequence number);
+    want[i]: the oracle's word on the connection."""
+    slots = [(M.CIPHER_AES_128_GCM, M.VERSION_TLS1_3, prng_bytes(401, 16), prng_bytes(402, 12), 1),
+             (M.CIPHER_AES_256_GCM, M.VERSION_TLS1_2, prng_bytes(403, 32), prng_bytes(404, 12), 1),
+             (M.CIPHER_CHACHA20_POLY1305, M.VERSION_TLS1_3, prng_bytes(405, 32), prng_bytes(406, 12), 1),
+             (M.CIPHER_CHACHA20_POLY1305, M.VERSION_TLS1_2, prng_bytes(407, 32), prng_bytes(408, 12), 1)]
+    ot = [O.Transform(v, c, k, k, iv, iv, granularity=g) for c, v, k, iv, g in slots]
+
+    def records(slot, i, ctr0, n, varying):
+        if n == 0:
+            return []
+        if not varying:
+            size = 1 + (3 * i) % 40
+            st, w, nrec, _ = O.stream_encrypt(ot[slot], prng_bytes(5000 + i, n * size), 23, ctr0.to_bytes(8, "big"), size)
+            assert st == 0 and nrec == n
+            return _split(w)
+        out = []
+        for k in range(n):
+            size = 1 + (i + 7 * k) % 40
+            st, w, nrec, _ = O.stream_encrypt(ot[slot], prng_bytes(5000 + i + 600 * k, size), 23,
+                                              (ctr0 + k).to_bytes(8, "big"), size)
+            assert st == 0 and nrec == 1
+            out.append(w)
+        assert all(len(a) != len(b) for a, b in zip(out, out[1:]))
+        return out
+
+    conns, framed, want, seen = [], [], [], set()
+    for i in range(MIX_N):
+        slot, ctr0 = (i // 20) % 4, 1000 + 7 * i
+        tls13 = slots[slot][1] == M.VERSION_TLS1_3
+        if i in MIX_BAD:
+            slot, tls13 = 1, False
+            recs = records(slot, i, ctr0, 3, True)
+            tail = {"type-first": None, "type-later": bytes([25, 3, 3, 0, 20]) + bytes(25),
+                    "short-header": bytes([23, 3, 3, 0]), "short-body": bytes([23, 3, 3, 0, 40]) + bytes(10),
+                    "too-long": bytes([23, 3, 3, 0x40, 0x21]) + bytes(60)}[MIX_BAD[i]]
+            if tail is None:
+                recs, tail = [], bytes([25, 3, 3, 0, 20]) + bytes(25) + b"".join(recs)
+        else:
+            n, varying = MIX_COUNTS[i % 10], (i // 10) % 2 == 1
+            recs, tail = records(slot, i, ctr0, n, varying), b""
+            ccs = (i // 80) % 4 if tls13 else 0
+            if ccs:
+                at = {1: 0, 2: len(recs) // 2, 3: len(recs)}[ccs]
+                recs = recs[:at] + [CCS] + recs[at:]
+            seen.add((n, varying, tls13, ccs))
+        pos, seq, fr = 0, ctr0, []
+        for r in recs:
+            fr.append((pos, r[0], seq))
+            pos += len(r)
+            seq += 0 if (tls13 and r[0] == 20) else 1
+        data = b"".join(recs) + tail
+        conns.append((slot, data, ctr0, 0))
+        framed.append(fr)
+        want.append(O.stream_decrypt(ot[slot], data, ctr0.to_bytes(8, "big"), 0))
+    assert {(n, v, True, c) for n in MIX_COUNTS for v in (False, True) for c in (1, 2, 3)} <= seen
+    assert {(n, v, False, 0) for n in MIX_COUNTS for v in (False, True)} <= seen
+    return slots, conns, framed, want
+
+
+@pytest.mark.parametrize("fr", FRAMINGS, ids=FRAMING_IDS)
+def test_header_walk_mix_matches_oracle(fr, monkeypatch, launch_log):
+    """The header walk every receive framing shares (rx_count_conn /
+    rx_emit_conn at G = 1, 4, 8, 16, in three kernels and in one pass) over
+    _walk_mix(): per connection the oracle's status, records, bytes consumed
+    and counter; per framed record its descriptor -- position, sequence number
+    (a TLS 1.3 CCS takes none, the record after it the next one), slot (NO_SLOT
+    for that CCS) and type; and the launch log names the leg."""
+    _framing(monkeypatch, fr)
+    gw, grouped, fused, rg = fr
+    slots, conns, framed, want = _walk_mix()
+    c = Conns(slots)
+    launch_log.reset()
+    a, recs, res, sres, offs = c.decrypt(conns)
+    assert launch_log(_abi.LOG_STREAM_RX_FRAME) == \
+        [(_abi.LOG_STREAM_RX_FRAME, int(fused == "1" and gw == "1"), int(rg) if gw == "1" else 1, 0, 0)]
+    first = 0
+    for i, (slot, data, ctr0, _) in enumerate(conns):
+        w, wrecs, wbuf = want[i]
+        g = sres[i]
+        assert (int(g["status"]), int(g["nrec"]), int(g["consumed"]), bytes(g["in_ctr"]), int(g["nb_zero"])) == \
+            (w["status"], w["nrec"], w["consumed"], w["in_ctr"], w["nb_zero"]), (i, w)
+        assert (int(g["first"]), int(g["nparsed"])) == (first, len(framed[i])), i
+        tls13 = slots[slot][1] == M.VERSION_TLS1_3
+        for k, (pos, typ, seq) in enumerate(framed[i]):
+            d = recs[first + k]
+            assert (int(d["buf_off"]), bytes(d["ctr"]), int(d["slot"]), int(d["type"])) == \
+                (offs[i] + pos, seq.to_bytes(8, "big"), NO_SLOT if (tls13 and typ == 20) else slot, typ), (i, k)
+        for k, (off, doff, dlen, typ) in enumerate(wrecs):
+            rr = res[first + k]
+            assert (int(rr["data_offset"]), int(rr["data_len"]), int(rr["type"])) == (doff, dlen, typ), (i, k)
+            s0 = offs[i] + off + doff
+            assert a[s0:s0 + dlen].tobytes() == wbuf[off + doff:off + doff + dlen], (i, k)
+        first += len(framed[i])
     c.close()
 
 

@@ -420,6 +420,126 @@ typedef struct tlsrec_tls13_secret {
 int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                tlsrec_tls13_secret *secrets, int key_update, void *stream);
 
+/* ---- the rest of the TLS 1.3 ladder (RFC 8446 7.1) -----------------------
+ * Single-shot: the four helpers of ssl_tls13_keys.c:421-650, the Finished MAC
+ * and the PSK binder, with the reference's arguments.  `transcript` is the
+ * transcript hash (MBEDTLS_SSL_TLS1_3_CONTEXT_HASHED).  A hash_alg that is no
+ * PSA hash identifier returns TLSREC_ERR_SSL_INTERNAL_ERROR as the reference's
+ * assertion does; a hash other than SHA-256 / SHA-384, or a NULL pointer,
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA.  Fields are MBEDTLS_TLS1_3_MD_MAX_SIZE =
+ * PSA_HASH_MAX_SIZE = 64 bytes (ssl.h:672), the first Hash.length written. */
+#define TLSREC_TLS13_PSK_EXTERNAL   0     /* MBEDTLS_SSL_TLS1_3_PSK_EXTERNAL, ssl_tls13_keys.h:38 */
+#define TLSREC_TLS13_PSK_RESUMPTION 1     /* MBEDTLS_SSL_TLS1_3_PSK_RESUMPTION, ssl_tls13_keys.h:39 */
+
+/* mbedtls_ssl_tls13_early_secrets, library/ssl_misc.h:621-625 */
+typedef struct tlsrec_tls13_early_secrets {
+    unsigned char binder_key[64];
+    unsigned char client_early_traffic_secret[64];
+    unsigned char early_exporter_master_secret[64];
+} tlsrec_tls13_early_secrets;
+/* mbedtls_ssl_tls13_handshake_secrets, library/ssl_misc.h:627-630 */
+typedef struct tlsrec_tls13_handshake_secrets {
+    unsigned char client_handshake_traffic_secret[64];
+    unsigned char server_handshake_traffic_secret[64];
+} tlsrec_tls13_handshake_secrets;
+/* mbedtls_ssl_tls13_application_secrets, include/mbedtls/ssl.h:1085-1090 */
+typedef struct tlsrec_tls13_application_secrets {
+    unsigned char client_application_traffic_secret_N[64];
+    unsigned char server_application_traffic_secret_N[64];
+    unsigned char exporter_master_secret[64];
+    unsigned char resumption_master_secret[64];
+} tlsrec_tls13_application_secrets;
+
+/* mbedtls_ssl_tls13_derive_early_secrets, ssl_tls13_keys.c:421-477 ("c e traffic",
+ * "e exp master"; binder_key is left alone, as there) */
+int tlsrec_tls13_derive_early_secrets(int hash_alg, const unsigned char *early_secret,
+                                      const unsigned char *transcript, size_t transcript_len,
+                                      tlsrec_tls13_early_secrets *derived);
+/* mbedtls_ssl_tls13_derive_handshake_secrets, ssl_tls13_keys.c:479-543 */
+int tlsrec_tls13_derive_handshake_secrets(int hash_alg, const unsigned char *handshake_secret,
+                                          const unsigned char *transcript, size_t transcript_len,
+                                          tlsrec_tls13_handshake_secrets *derived);
+/* mbedtls_ssl_tls13_derive_application_secrets, ssl_tls13_keys.c:545-615
+ * (resumption_master_secret is left alone) */
+int tlsrec_tls13_derive_application_secrets(int hash_alg, const unsigned char *application_secret,
+                                            const unsigned char *transcript, size_t transcript_len,
+                                            tlsrec_tls13_application_secrets *derived);
+/* mbedtls_ssl_tls13_derive_resumption_master_secret, ssl_tls13_keys.c:621-650
+ * (writes resumption_master_secret only) */
+int tlsrec_tls13_derive_resumption_master_secret(int hash_alg, const unsigned char *application_secret,
+                                                 const unsigned char *transcript, size_t transcript_len,
+                                                 tlsrec_tls13_application_secrets *derived);
+/* ssl_tls13_calc_finished_core, ssl_tls13_keys.c:697-768: finished_key =
+ * HKDF-Expand-Label(base_secret, "finished", "", Hash.length), out = HMAC(finished_key,
+ * transcript); base_secret and transcript are Hash.length bytes, *out_len = Hash.length */
+int tlsrec_tls13_calc_finished(int hash_alg, const unsigned char *base_secret,
+                               const unsigned char *transcript, unsigned char *out, size_t *out_len);
+/* mbedtls_ssl_tls13_create_psk_binder, ssl_tls13_keys.c:832-917 (without the ssl
+ * context, which it uses for debug output only): Early Secret from the PSK, the
+ * binder key under "res binder" (TLSREC_TLS13_PSK_RESUMPTION) or "ext binder" (any
+ * other psk_type), then the Finished MAC over `transcript`; Hash.length bytes to result */
+int tlsrec_tls13_create_psk_binder(int hash_alg, const unsigned char *psk, size_t psk_len, int psk_type,
+                                   const unsigned char *transcript, unsigned char *result);
+
+/* One TLS 1.3 connection at its ServerHello: 176 bytes, device-resident, only read */
+typedef struct tlsrec_tls13_hs_conn {
+    uint8_t psk[48];         /* psk_len bytes used */
+    uint8_t shared[80];      /* (EC)DHE shared secret, shared_len bytes used */
+    uint8_t transcript[48];  /* Hash(ClientHello..ServerHello), Hash.length bytes used */
+} tlsrec_tls13_hs_conn;
+
+/* Batch, handshake stage.  For each of `count` connections, in one kernel:
+ *   Early Secret = Extract(0, PSK)            (psk_len == 0: Hash.length zero bytes, as
+ *                                              tlsrec_tls13_evolve_secret takes a NULL input)
+ *   Handshake Secret = Extract(Derive-Secret(., "derived", ""), shared)
+ *                                             (shared_len == 0: zero bytes again, psk_ke)
+ *   c hs traffic / s hs traffic over `transcript`     -> hs_traffic[2i], [2i + 1]
+ *   their "finished" keys                             -> finished_keys[2i], [2i + 1] (may be NULL)
+ *   their key / iv                                    -> slots first + 2i (client_write), first + 2i + 1
+ *   Master Secret = Extract(Derive-Secret(., "derived", ""), 0)   -> master[i]
+ * The slots are loaded as TLS 1.3 keys of `cipher` (tls_minor 4, fixed_ivlen 12); the
+ * hash follows the cipher as in tlsrec_tls13_keytab_derive, which also names the
+ * accepted cipher ids; slot numbering as tlsrec_tls12_keytab_derive.  psk_len (0..48)
+ * and shared_len hold for the whole call.  The one divergence: shared_len is one of
+ * 0, 32 (x25519, secp256r1), 48 (secp384r1), 56 (x448), 66 (secp521r1); the FFDH
+ * groups' lengths are TLSREC_ERR_SSL_FEATURE_UNAVAILABLE here and stay with the
+ * single-shot calls.  Every output is a device array; the first Hash.length bytes of
+ * a 48-byte element are the value, the rest is written as zero.  Asynchronous on
+ * `stream`, no host round trip; conns must stay valid until the stream reaches it.
+ * Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for kt NULL, for conns,
+ * hs_traffic or master NULL with count != 0, for psk_len > 48, for [first, first +
+ * 2*count) overflowing or running past the table; TLSREC_ERR_SSL_FEATURE_UNAVAILABLE
+ * for an unknown cipher, then for another shared_len.  count == 0 then returns 0. */
+int tlsrec_tls13_keytab_derive_handshake(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                         uint32_t psk_len, uint32_t shared_len, const tlsrec_tls13_hs_conn *conns,
+                                         tlsrec_tls13_secret *hs_traffic, tlsrec_tls13_secret *finished_keys,
+                                         tlsrec_tls13_secret *master, void *stream);
+
+/* Batch, application stage: from master[i] and transcripts[i] = Hash(ClientHello..server
+ * Finished), c ap traffic -> app_traffic[2i], s ap traffic -> app_traffic[2i + 1], exp
+ * master -> exporter[i] (may be NULL), and the two directions' key / iv into the slot
+ * pair of the handshake stage.  app_traffic is in slot order, so a KeyUpdate of all of
+ * them is tlsrec_tls13_keytab_derive(kt, first, 2*count, cipher, app_traffic, 1, stream).
+ * Errors as above (master, transcripts or app_traffic NULL with count != 0). */
+int tlsrec_tls13_keytab_derive_application(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                           const tlsrec_tls13_secret *master, const tlsrec_tls13_secret *transcripts,
+                                           tlsrec_tls13_secret *app_traffic, tlsrec_tls13_secret *exporter,
+                                           void *stream);
+/* Batch: out[i] = HMAC(finished_keys[i], transcripts[i]), the verify_data of a Finished
+ * message (RFC 8446 4.4.4).  TLSREC_ERR_SSL_BAD_INPUT_DATA for a hash other than
+ * SHA-256 / SHA-384, then for a NULL array with count != 0; count == 0 returns 0. */
+int tlsrec_tls13_batch_verify_data(int hash_alg, const tlsrec_tls13_secret *finished_keys,
+                                   const tlsrec_tls13_secret *transcripts, tlsrec_tls13_secret *out,
+                                   uint32_t count, void *stream);
+/* Batch: out[i] = Derive-Secret(secrets[i], label, .) with the hashed context
+ * transcripts[i] of Hash.length bytes, e.g. "res master" over Hash(ClientHello..client
+ * Finished).  The batch takes a label of at most 12 bytes (every label of RFC 8446 7.1
+ * fits); a longer one, or a NULL label with label_len != 0, is
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA, checked first; then as tlsrec_tls13_batch_verify_data. */
+int tlsrec_tls13_batch_derive_secret(int hash_alg, const unsigned char *label, size_t label_len,
+                                     const tlsrec_tls13_secret *secrets, const tlsrec_tls13_secret *transcripts,
+                                     tlsrec_tls13_secret *out, uint32_t count, void *stream);
+
 /* ---- TLS 1.2 / DTLS 1.2 key derivation (library/ssl_tls.c) ---------------
  * The TLS 1.2 PRF (RFC 5246 section 5, P_SHA256 / P_SHA384) on the GPU: the
  * reference's single-shot functions, and a batch that expands many

@@ -68,6 +68,7 @@ ALG_SHA_256 = 0x02000009      # PSA_ALG_SHA_256
 ALG_SHA_384 = 0x0200000a      # PSA_ALG_SHA_384
 TLS13_CONTEXT_UNHASHED = 0
 TLS13_CONTEXT_HASHED = 1
+TLS13_PSK_EXTERNAL, TLS13_PSK_RESUMPTION = 0, 1             # ssl_tls13_keys.h:38-39
 TLS_PRF_NONE, TLS_PRF_SHA384, TLS_PRF_SHA256 = 0, 1, 2      # mbedtls_tls_prf_types, ssl.h:1254-1256
 IS_CLIENT, IS_SERVER = 0, 1                                 # MBEDTLS_SSL_IS_CLIENT / _SERVER
 
@@ -138,6 +139,36 @@ class CKeySet(ctypes.Structure):
 class CTls12Conn(ctypes.Structure):
     """tlsrec_tls12_conn: one TLS 1.2 / DTLS 1.2 connection after its handshake (112 bytes)"""
     _fields_ = [("master", ctypes.c_ubyte * 48), ("randbytes", ctypes.c_ubyte * 64)]
+
+
+class CTls13Secret(ctypes.Structure):
+    """tlsrec_tls13_secret: one secret of the TLS 1.3 ladder (48 bytes, Hash.length used)"""
+    _fields_ = [("secret", ctypes.c_ubyte * 48)]
+
+
+class CTls13HsConn(ctypes.Structure):
+    """tlsrec_tls13_hs_conn: one TLS 1.3 connection at its ServerHello (176 bytes)"""
+    _fields_ = [("psk", ctypes.c_ubyte * 48), ("shared", ctypes.c_ubyte * 80), ("transcript", ctypes.c_ubyte * 48)]
+
+
+_MD_MAX = ctypes.c_ubyte * 64      # MBEDTLS_TLS1_3_MD_MAX_SIZE
+
+
+class CTls13EarlySecrets(ctypes.Structure):
+    """mbedtls_ssl_tls13_early_secrets (library/ssl_misc.h:621-625)"""
+    _fields_ = [("binder_key", _MD_MAX), ("client_early_traffic_secret", _MD_MAX),
+                ("early_exporter_master_secret", _MD_MAX)]
+
+
+class CTls13HandshakeSecrets(ctypes.Structure):
+    """mbedtls_ssl_tls13_handshake_secrets (library/ssl_misc.h:627-630)"""
+    _fields_ = [("client_handshake_traffic_secret", _MD_MAX), ("server_handshake_traffic_secret", _MD_MAX)]
+
+
+class CTls13ApplicationSecrets(ctypes.Structure):
+    """mbedtls_ssl_tls13_application_secrets (include/mbedtls/ssl.h:1085-1090)"""
+    _fields_ = [("client_application_traffic_secret_N", _MD_MAX), ("server_application_traffic_secret_N", _MD_MAX),
+                ("exporter_master_secret", _MD_MAX), ("resumption_master_secret", _MD_MAX)]
 
 
 class CTicketKeys(ctypes.Structure):
@@ -254,6 +285,16 @@ SIGNATURES = {
     "tlsrec_tls13_exporter": (_INT, [_INT, _VP, _SZ, _VP, _SZ, _VP, _SZ, _VP, _SZ]),
     "tlsrec_tls13_update_traffic_secret": (_INT, [_INT, _VP, _VP]),
     "tlsrec_tls13_keytab_derive": (_INT, [_VP, _U32, _U32, _INT, _VP, _INT, _VP]),
+    "tlsrec_tls13_derive_early_secrets": (_INT, [_INT, _VP, _VP, _SZ, _VP]),
+    "tlsrec_tls13_derive_handshake_secrets": (_INT, [_INT, _VP, _VP, _SZ, _VP]),
+    "tlsrec_tls13_derive_application_secrets": (_INT, [_INT, _VP, _VP, _SZ, _VP]),
+    "tlsrec_tls13_derive_resumption_master_secret": (_INT, [_INT, _VP, _VP, _SZ, _VP]),
+    "tlsrec_tls13_calc_finished": (_INT, [_INT, _VP, _VP, _VP, _VP]),
+    "tlsrec_tls13_create_psk_binder": (_INT, [_INT, _VP, _SZ, _INT, _VP, _VP]),
+    "tlsrec_tls13_keytab_derive_handshake": (_INT, [_VP, _U32, _U32, _INT, _U32, _U32, _VP, _VP, _VP, _VP, _VP]),
+    "tlsrec_tls13_keytab_derive_application": (_INT, [_VP, _U32, _U32, _INT, _VP, _VP, _VP, _VP, _VP]),
+    "tlsrec_tls13_batch_verify_data": (_INT, [_INT, _VP, _VP, _VP, _U32, _VP]),
+    "tlsrec_tls13_batch_derive_secret": (_INT, [_INT, _VP, _SZ, _VP, _VP, _VP, _U32, _VP]),
     "tlsrec_tls_prf": (_INT, [_INT, _VP, _SZ, ctypes.c_char_p, _VP, _SZ, _VP, _SZ]),
     "tlsrec_tls12_compute_master": (_INT, [_INT, _VP, _SZ, _VP, _SZ, _INT, _VP]),
     "tlsrec_tls12_split_key_block": (_INT, [_INT, _VP, _SZ, _VP]),

@@ -14,6 +14,14 @@
  *   "traffic upd" (ssl_tls13_keys.h:16)         tlsrec_tls13_update_traffic_secret (RFC 8446 7.2)
  *   (batch)                                     tlsrec_tls13_keytab_derive: secrets in HBM ->
  *                                               key material -> key-table slots, no host round trip
+ *   ..._derive_early / _handshake / _application_secrets,
+ *   ..._derive_resumption_master_secret :421-650 tlsrec_tls13_derive_*_secrets, ..._resumption_master_secret
+ *   ssl_tls13_calc_finished_core        :697    tlsrec_tls13_calc_finished
+ *   mbedtls_ssl_tls13_create_psk_binder :832    tlsrec_tls13_create_psk_binder
+ *   (batch)                                     tlsrec_tls13_keytab_derive_handshake, _application,
+ *                                               tlsrec_tls13_batch_verify_data, _batch_derive_secret:
+ *                                               the ladder from PSK / (EC)DHE secret to the application
+ *                                               keys, written for its fixed shapes like the TLS 1.2 batch
  *
  * Every hash, HMAC and HKDF step runs in a kernel; the host only encodes the
  * HkdfLabel byte string (length, "tls13 " + label, context length), moves
@@ -787,6 +795,474 @@ template <int ALG, int KL, int ML> __global__ void __launch_bounds__(64) tls12_d
     for (int j = 0; j < 12; j++) M[j] = 0;
 }
 
+/* ---------------- TLS 1.3 ladder, batch ----------------------------------
+ * Early Secret -> Handshake Secret -> handshake traffic keys and Finished
+ * keys -> Master Secret -> application traffic keys (RFC 8446 7.1; the helpers
+ * of ssl_tls13_keys.c:421-650 and ssl_tls13_calc_finished_core :697), one
+ * connection per lane.  As in the TLS 1.2 kernels nothing goes through Hash /
+ * put(): every message here is a single inner block whose words are put
+ * together with constant indices -- an HkdfLabel with a label of at most 12
+ * characters and a context of H bytes, || 0x01, is at most 55 bytes (SHA-256)
+ * or 71 (SHA-384) -- except the Extract over a 56- or 66-byte shared secret
+ * under SHA-256, which takes a second one.  The HMAC midstates of a secret are
+ * computed once and serve every Expand under it; the midstates of the zero
+ * salt, Hash("") and, for a connection without a PSK, the midstates of
+ * Derive-Secret(Early Secret, "derived", "") are the same for every connection
+ * and arrive as kernel arguments (LadderConsts, scalar registers).
+ *
+ * Messages are addressed in 32-bit big-endian cells: 16 to a SHA-256 block, 32
+ * to a SHA-512 one. */
+struct L256 {
+    typedef S256 S;
+    typedef uint32_t W;
+    enum { HW = 8, HC = 8, HB = 32, BB = 64, LENB = 8 };
+    static __device__ __forceinline__ W iv(int j)
+    {
+        const W t[8] = { 0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                         0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u };
+        return t[j];
+    }
+};
+struct L384 {
+    typedef S512 S;
+    typedef uint64_t W;
+    enum { HW = 6, HC = 12, HB = 48, BB = 128, LENB = 16 };
+    static __device__ __forceinline__ W iv(int j)
+    {
+        const W t[8] = { 0xcbbb9d5dc1059ed8ULL, 0x629a292a367cd507ULL, 0x9159015a3070dd17ULL,
+                         0x152fecd8f70e5939ULL, 0x67332667ffc00b31ULL, 0x8eb44a8768581511ULL,
+                         0xdb0c2e0d64f98fa7ULL, 0x47b5481dbefa4fa4ULL };
+        return t[j];
+    }
+};
+
+/* the constants of one hash (values in ladder_consts() on the host side) */
+template <class T> struct LadderConsts {
+    typename T::W zero_ip[8], zero_op[8];   /* HMAC midstates of a salt of H zero bytes */
+    typename T::W d0_ip[8], d0_op[8];       /* ... of Derive-Secret(Extract(0, 0), "derived", "") */
+    typename T::W empty[T::HW];             /* Hash("") */
+};
+
+/* An HkdfLabel up to and including its context-length byte (ssl_tls13_keys.c:98-136)
+ * as big-endian cells, zero-padded: 10 + label_len <= 22 bytes.  Encoded on the host. */
+struct LabelW { uint32_t c[6]; };
+
+/* cell i of a block / of a digest; i is a constant wherever these are used */
+template <class T> __device__ __forceinline__ void or_cell(typename T::W (&w)[16], int i, uint32_t v)
+{
+    if constexpr (sizeof(typename T::W) == 4) w[i] |= v;
+    else w[i >> 1] |= (uint64_t) v << ((i & 1) ? 0 : 32);
+}
+template <class T, int N> __device__ __forceinline__ uint32_t cell(const typename T::W (&x)[N], int i)
+{
+    if constexpr (sizeof(typename T::W) == 4) return x[i];
+    else return (i & 1) ? (uint32_t) x[i >> 1] : (uint32_t) (x[i >> 1] >> 32);
+}
+/* the 4 bytes of v at byte position p of the block */
+template <class T> __device__ __forceinline__ void or_cell_at(typename T::W (&w)[16], int p, uint32_t v)
+{
+    const int i = p >> 2, r = p & 3;
+    or_cell<T>(w, i, r ? v >> (8 * r) : v);
+    if (r) or_cell<T>(w, i + 1, v << (32 - 8 * r));
+}
+template <class T> __device__ __forceinline__ void or_byte_at(typename T::W (&w)[16], int p, uint32_t b)
+{
+    or_cell<T>(w, p >> 2, b << (24 - 8 * (p & 3)));
+}
+
+/* the two midstates of HMAC under an H-byte key: 2 compressions */
+template <class T>
+__device__ __forceinline__ void hmac_mid(const typename T::W (&key)[T::HW], typename T::W (&ip)[8], typename T::W (&op)[8])
+{
+    typedef typename T::W W;
+    W w[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = (j < T::HW ? key[j] : (W) 0) ^ (W) 0x3636363636363636ULL;
+#pragma unroll
+    for (int j = 0; j < 8; j++) ip[j] = T::iv(j);
+    sha_compress<typename T::S>(ip, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = (j < T::HW ? key[j] : (W) 0) ^ (W) 0x5c5c5c5c5c5c5c5cULL;
+#pragma unroll
+    for (int j = 0; j < 8; j++) op[j] = T::iv(j);
+    sha_compress<typename T::S>(op, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
+/* the outer hash: opad midstate over the inner digest in st (consumed): 1 compression */
+template <class T>
+__device__ __forceinline__ void hmac_outer(const typename T::W (&op)[8], typename T::W (&st)[8], typename T::W (&out)[T::HW])
+{
+    typedef typename T::W W;
+    W w[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = j < T::HW ? st[j] : (W) 0;
+    w[T::HW] = (W) 0x80 << (8 * sizeof(W) - 8);
+    w[15] = (T::BB + T::HB) * 8;
+#pragma unroll
+    for (int j = 0; j < 8; j++) st[j] = op[j];
+    sha_compress<typename T::S>(st, w);
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) out[j] = st[j];
+#pragma unroll
+    for (int j = 0; j < 8; j++) st[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
+/* HMAC of a message that is the one inner block w (padding and length in place; consumed): 2 compressions */
+template <class T>
+__device__ __forceinline__ void hmac_block(const typename T::W (&ip)[8], const typename T::W (&op)[8],
+                                           typename T::W (&w)[16], typename T::W (&out)[T::HW])
+{
+    typename T::W st[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) st[j] = ip[j];
+    sha_compress<typename T::S>(st, w);
+    hmac_outer<T>(op, st, out);
+}
+
+/* the inner block of an H-byte message (an Extract over a secret or over H zero bytes, a Finished MAC) */
+template <class T> __device__ __forceinline__ void digest_block(typename T::W (&w)[16], const typename T::W (&x)[T::HW])
+{
+    typedef typename T::W W;
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = j < T::HW ? x[j] : (W) 0;
+    w[T::HW] = (W) 0x80 << (8 * sizeof(W) - 8);
+    w[15] = (T::BB + T::HB) * 8;
+}
+
+/* the inner block of HKDF-Expand-Label's one HMAC: HkdfLabel (OFF bytes up to
+ * the context, then the H-byte context if CTX) || 0x01 */
+template <class T, int OFF, bool CTX>
+__device__ __forceinline__ void label_block(typename T::W (&w)[16], const LabelW &lb, const typename T::W (&ctx)[T::HW])
+{
+    constexpr int END = OFF + (CTX ? (int) T::HB : 0);
+    static_assert(OFF <= 22 && END + 2 + T::LENB <= T::BB, "HkdfLabel || 0x01 pads into one block");
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int c = 0; c < (OFF + 3) / 4; c++) or_cell<T>(w, c, lb.c[c]);
+    if constexpr (CTX) {
+#pragma unroll
+        for (int c = 0; c < T::HC; c++) or_cell_at<T>(w, OFF + 4 * c, cell<T, T::HW>(ctx, c));
+    }
+    or_byte_at<T>(w, END, 0x01);
+    or_byte_at<T>(w, END + 1, 0x80);
+    w[15] = (T::BB + END + 1) * 8;
+}
+
+/* block `blk` of a message of n bytes (n wave-uniform, n + 1 + LENB <= 2 * BB)
+ * held in the cells m[]: bytes past n are masked off, 0x80 follows the message
+ * and the length closes the last block */
+template <class T, int NC>
+__device__ __forceinline__ void msg_block(typename T::W (&w)[16], const uint32_t (&m)[NC], uint32_t n, int blk)
+{
+    constexpr int CPB = T::BB / 4;
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int c = 0; c < CPB; c++) {
+        const int g = blk * CPB + c;              /* blk is 0 or 1 at every call: g is a constant */
+        const int rem = (int) n - 4 * g;
+        const uint32_t v = g < NC ? m[g] : 0u;
+        uint32_t x;
+        if (rem >= 4) x = v;
+        else if (rem > 0) x = (v & ~(0xffffffffu >> (8 * rem))) | (0x80u << (24 - 8 * rem));
+        else x = rem == 0 ? 0x80000000u : 0u;
+        or_cell<T>(w, c, x);
+    }
+    if ((int) n + 1 + (int) T::LENB <= (blk + 1) * (int) T::BB) w[15] = (typename T::W) ((T::BB + n) * 8);
+}
+
+/* NC cells from device memory: 16-byte loads, or bytes when the array is not 16-byte aligned */
+template <int NC> __device__ __forceinline__ void load_cells(const uint8_t *p, bool aligned, uint32_t (&m)[NC])
+{
+    if (aligned) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(p);
+#pragma unroll
+        for (int k = 0; k < (NC + 3) / 4; k++) {
+            const uint4 v = q[k];
+            const uint32_t x[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (4 * k + j < NC) m[4 * k + j] = __builtin_bswap32(x[j]);
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < NC; n++) m[n] = load_be32(p + 4 * n, false);
+    }
+}
+
+template <class T> __device__ __forceinline__ void load_digest(const uint8_t *p, bool aligned, typename T::W (&x)[T::HW])
+{
+    uint32_t m[T::HC];
+    load_cells<T::HC>(p, aligned, m);
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) {
+        if constexpr (sizeof(typename T::W) == 4) x[j] = m[j];
+        else x[j] = ((uint64_t) m[2 * j] << 32) | m[2 * j + 1];
+    }
+#pragma unroll
+    for (int j = 0; j < T::HC; j++) m[j] = 0;
+}
+
+/* a tlsrec_tls13_secret: H bytes of x, the rest zero; three 16-byte stores, or bytes */
+template <class T> __device__ __forceinline__ void store_secret(tlsrec_tls13_secret *dst, bool aligned, const typename T::W (&x)[T::HW])
+{
+    uint32_t m[12];
+#pragma unroll
+    for (int c = 0; c < 12; c++) m[c] = c < T::HC ? __builtin_bswap32(cell<T, T::HW>(x, c)) : 0u;
+    if (aligned) {
+        uint4 *q = reinterpret_cast<uint4 *>(dst);
+#pragma unroll
+        for (int k = 0; k < 3; k++) q[k] = make_uint4(m[4 * k], m[4 * k + 1], m[4 * k + 2], m[4 * k + 3]);
+    } else {
+        uint8_t *b = dst->secret;
+#pragma unroll
+        for (int c = 0; c < 12; c++) {
+            b[4 * c] = (uint8_t) m[c]; b[4 * c + 1] = (uint8_t) (m[c] >> 8);
+            b[4 * c + 2] = (uint8_t) (m[c] >> 16); b[4 * c + 3] = (uint8_t) (m[c] >> 24);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 12; c++) m[c] = 0;
+}
+
+/* the labels of one stage, each with its Hash.length / key length / 12 as the
+ * output length and the context length it is used with */
+struct LadderLabels { LabelW derived, c_traffic, s_traffic, extra, key, iv, fin; };
+enum { OFF_DERIVED = 17, OFF_TRAFFIC = 22, OFF_EXP_MASTER = 20, OFF_KEY = 13, OFF_IV = 12, OFF_FINISHED = 18 };
+
+/* One direction under its traffic secret ts: write_key, write_iv
+ * (ssl_tls13_make_traffic_key, ssl_tls13_keys.c:219-246) as a
+ * tlsrec_key_material, and the Finished key if fin != NULL.  2 + 4 (+ 2)
+ * compressions. */
+template <class T>
+__device__ __forceinline__ void traffic_side(const typename T::W (&ts)[T::HW], const LadderLabels &lb, uint32_t head,
+                                             uint32_t key_cells, tlsrec_key_material *km_dst, tlsrec_tls13_secret *fin,
+                                             bool fin_aligned)
+{
+    typedef typename T::W W;
+    W ip[8], op[8], w[16], K[T::HW], V[T::HW];
+    hmac_mid<T>(ts, ip, op);
+    label_block<T, OFF_KEY, false>(w, lb.key, K);
+    hmac_block<T>(ip, op, w, K);
+    label_block<T, OFF_IV, false>(w, lb.iv, V);
+    hmac_block<T>(ip, op, w, V);
+    uint32_t km[16];
+    km[0] = head;
+#pragma unroll
+    for (int j = 1; j < 16; j++) km[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) km[4 + j] = __builtin_bswap32(cell<T, T::HW>(V, j));
+#pragma unroll
+    for (int j = 0; j < 8; j++) km[8 + j] = (uint32_t) j < key_cells ? __builtin_bswap32(cell<T, T::HW>(K, j)) : 0u;
+    uint4 *dst = reinterpret_cast<uint4 *>(km_dst);
+#pragma unroll
+    for (int k = 0; k < 4; k++) dst[k] = make_uint4(km[4 * k], km[4 * k + 1], km[4 * k + 2], km[4 * k + 3]);
+    if (fin) {
+        label_block<T, OFF_FINISHED, false>(w, lb.fin, K);
+        hmac_block<T>(ip, op, w, K);
+        store_secret<T>(fin, fin_aligned, K);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; j++) km[j] = 0;
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) { K[j] = 0; V[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+}
+
+enum { AL_CONNS = 1, AL_TRAFFIC = 2, AL_AUX = 4, AL_MASTER = 8, AL_TRANSCRIPT = 16 };
+
+template <class T> struct Tls13HsArgs {
+    const tlsrec_tls13_hs_conn *conns;
+    tlsrec_key_material *out;             /* staging area of slot `first`: 2 records per connection */
+    tlsrec_tls13_secret *hs_traffic, *finished, *master;
+    uint32_t count, head, key_cells, psk_len, shared_len, aligned;
+    LadderConsts<T> k;
+    LadderLabels lb;
+};
+
+/* Compressions per connection: no PSK 0, a PSK 8 (Extract 2,
+ * midstates 2, "derived" 2, midstates 2); Extract over the shared secret 2 (3
+ * for 56 / 66 bytes under SHA-256); midstates 2; two traffic secrets 4;
+ * "derived" 2, midstates 2, Master Secret 2; each direction 2 + key 2 + iv 2 +
+ * finished 2: 30 / 38 with both Finished keys, 26 / 34 without. */
+template <class T> __global__ void __launch_bounds__(64) tls13_hs_kernel(Tls13HsArgs<T> a)
+{
+    typedef typename T::W W;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    const uint8_t *conn = reinterpret_cast<const uint8_t *>(a.conns + i);
+    const bool cal = (a.aligned & AL_CONNS) != 0;
+    W ip[8], op[8], w[16], x[T::HW];
+    if (a.psk_len) {
+        /* Early Secret = Extract(0, PSK); then the salt of the next Extract */
+        uint32_t P[12];
+        load_cells<12>(conn, cal, P);
+        msg_block<T, 12>(w, P, a.psk_len, 0);
+        hmac_block<T>(a.k.zero_ip, a.k.zero_op, w, x);
+        hmac_mid<T>(x, ip, op);
+        label_block<T, OFF_DERIVED, true>(w, a.lb.derived, a.k.empty);
+        hmac_block<T>(ip, op, w, x);
+        hmac_mid<T>(x, ip, op);
+#pragma unroll
+        for (int j = 0; j < 12; j++) P[j] = 0;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) { ip[j] = a.k.d0_ip[j]; op[j] = a.k.d0_op[j]; }
+    }
+    /* Handshake Secret = Extract(., shared), H zero bytes for psk_ke */
+    {
+        W st[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        if (a.shared_len) {
+            uint32_t Sh[20];
+            load_cells<20>(conn + 48, cal, Sh);
+            msg_block<T, 20>(w, Sh, a.shared_len, 0);
+            sha_compress<typename T::S>(st, w);
+            if (a.shared_len + 1 + T::LENB > T::BB) {
+                msg_block<T, 20>(w, Sh, a.shared_len, 1);
+                sha_compress<typename T::S>(st, w);
+            }
+#pragma unroll
+            for (int j = 0; j < 20; j++) Sh[j] = 0;
+        } else {
+#pragma unroll
+            for (int j = 0; j < T::HW; j++) x[j] = 0;
+            digest_block<T>(w, x);
+            sha_compress<typename T::S>(st, w);
+        }
+        hmac_outer<T>(op, st, x);
+    }
+    hmac_mid<T>(x, ip, op);
+    W tr[T::HW], cs[T::HW], ss[T::HW];
+    load_digest<T>(conn + 128, cal, tr);
+    label_block<T, OFF_TRAFFIC, true>(w, a.lb.c_traffic, tr);
+    hmac_block<T>(ip, op, w, cs);
+    label_block<T, OFF_TRAFFIC, true>(w, a.lb.s_traffic, tr);
+    hmac_block<T>(ip, op, w, ss);
+    /* Master Secret = Extract(Derive-Secret(Handshake Secret, "derived", ""), 0) */
+    label_block<T, OFF_DERIVED, true>(w, a.lb.derived, a.k.empty);
+    hmac_block<T>(ip, op, w, x);
+    hmac_mid<T>(x, ip, op);
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) x[j] = 0;
+    digest_block<T>(w, x);
+    hmac_block<T>(ip, op, w, x);
+    store_secret<T>(a.master + i, (a.aligned & AL_MASTER) != 0, x);
+    store_secret<T>(a.hs_traffic + 2 * (size_t) i, (a.aligned & AL_TRAFFIC) != 0, cs);
+    store_secret<T>(a.hs_traffic + 2 * (size_t) i + 1, (a.aligned & AL_TRAFFIC) != 0, ss);
+#pragma unroll 1
+    for (int side = 0; side < 2; side++) {
+#pragma unroll
+        for (int j = 0; j < T::HW; j++) x[j] = side ? ss[j] : cs[j];
+        traffic_side<T>(x, a.lb, a.head, a.key_cells, a.out + 2 * (size_t) i + side,
+                        a.finished ? a.finished + 2 * (size_t) i + side : nullptr, (a.aligned & AL_AUX) != 0);
+    }
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) { x[j] = 0; cs[j] = 0; ss[j] = 0; tr[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
+template <class T> struct Tls13AppArgs {
+    const tlsrec_tls13_secret *master, *transcripts;
+    tlsrec_key_material *out;
+    tlsrec_tls13_secret *app_traffic, *exporter;
+    uint32_t count, head, key_cells, aligned;
+    LadderLabels lb;                      /* extra: "exp master" */
+};
+
+/* Compressions per connection: midstates 2, two traffic secrets 4, exporter
+ * master secret 2, each direction 2 + key 2 + iv 2: 20, 18 without the exporter. */
+template <class T> __global__ void __launch_bounds__(64) tls13_app_kernel(Tls13AppArgs<T> a)
+{
+    typedef typename T::W W;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    W ip[8], op[8], w[16], x[T::HW], tr[T::HW], cs[T::HW], ss[T::HW];
+    load_digest<T>(a.master[i].secret, (a.aligned & AL_MASTER) != 0, x);
+    load_digest<T>(a.transcripts[i].secret, (a.aligned & AL_TRANSCRIPT) != 0, tr);
+    hmac_mid<T>(x, ip, op);
+    label_block<T, OFF_TRAFFIC, true>(w, a.lb.c_traffic, tr);
+    hmac_block<T>(ip, op, w, cs);
+    label_block<T, OFF_TRAFFIC, true>(w, a.lb.s_traffic, tr);
+    hmac_block<T>(ip, op, w, ss);
+    if (a.exporter) {
+        label_block<T, OFF_EXP_MASTER, true>(w, a.lb.extra, tr);
+        hmac_block<T>(ip, op, w, x);
+        store_secret<T>(a.exporter + i, (a.aligned & AL_AUX) != 0, x);
+    }
+    store_secret<T>(a.app_traffic + 2 * (size_t) i, (a.aligned & AL_TRAFFIC) != 0, cs);
+    store_secret<T>(a.app_traffic + 2 * (size_t) i + 1, (a.aligned & AL_TRAFFIC) != 0, ss);
+#pragma unroll 1
+    for (int side = 0; side < 2; side++) {
+#pragma unroll
+        for (int j = 0; j < T::HW; j++) x[j] = side ? ss[j] : cs[j];
+        traffic_side<T>(x, a.lb, a.head, a.key_cells, a.out + 2 * (size_t) i + side, nullptr, false);
+    }
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) { x[j] = 0; cs[j] = 0; ss[j] = 0; tr[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
+/* out[i] = HMAC(keys[i], msgs[i]) over H-byte messages (verify_data under a
+ * Finished key), or with label_len != ~0u Expand-Label(keys[i], label, msgs[i], H)
+ * (Derive-Secret with a hashed context): 4 compressions either way. */
+struct Tls13MacArgs {
+    const tlsrec_tls13_secret *keys, *msgs;
+    tlsrec_tls13_secret *out;
+    uint32_t count, aligned, label_len;   /* AL_MASTER keys, AL_TRANSCRIPT msgs, AL_AUX out */
+    LabelW label;
+};
+enum : uint32_t { MAC_PLAIN = ~0u };
+
+template <class T> __global__ void __launch_bounds__(64) tls13_mac_kernel(Tls13MacArgs a)
+{
+    typedef typename T::W W;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    W ip[8], op[8], w[16], x[T::HW], m[T::HW];
+    load_digest<T>(a.keys[i].secret, (a.aligned & AL_MASTER) != 0, x);
+    load_digest<T>(a.msgs[i].secret, (a.aligned & AL_TRANSCRIPT) != 0, m);
+    hmac_mid<T>(x, ip, op);
+    /* the label's length only moves the context inside the block: wave-uniform */
+    switch (a.label_len) {
+        case 0: label_block<T, 10, true>(w, a.label, m); break;
+        case 1: label_block<T, 11, true>(w, a.label, m); break;
+        case 2: label_block<T, 12, true>(w, a.label, m); break;
+        case 3: label_block<T, 13, true>(w, a.label, m); break;
+        case 4: label_block<T, 14, true>(w, a.label, m); break;
+        case 5: label_block<T, 15, true>(w, a.label, m); break;
+        case 6: label_block<T, 16, true>(w, a.label, m); break;
+        case 7: label_block<T, 17, true>(w, a.label, m); break;
+        case 8: label_block<T, 18, true>(w, a.label, m); break;
+        case 9: label_block<T, 19, true>(w, a.label, m); break;
+        case 10: label_block<T, 20, true>(w, a.label, m); break;
+        case 11: label_block<T, 21, true>(w, a.label, m); break;
+        case 12: label_block<T, 22, true>(w, a.label, m); break;
+        default: digest_block<T>(w, m); break;
+    }
+    hmac_block<T>(ip, op, w, x);
+    store_secret<T>(a.out + i, (a.aligned & AL_AUX) != 0, x);
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) { x[j] = 0; m[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
 } /* namespace tlsks */
 
 using namespace tlsks;
@@ -1147,6 +1623,360 @@ extern "C" int tlsrec_tls13_keytab_derive(tlsrec_keytab *kt, uint32_t first, uin
     int r = tlsrec__tls13_stage_keys(kt, first, count, cipher, secrets, key_update, stream);
     if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, count, cipher, (hipStream_t) stream);
     return r;
+}
+
+/* ---- the rest of the ladder, single-shot (ssl_tls13_keys.c:421-650, :697, :832) ----
+ * Compositions of the calls above on the kdf_job_kernel path. */
+static int ladder_alg(int hash_alg, int *a)
+{
+    /* the reference's "!PSA_ALG_IS_HASH(hash_alg)" assertion, then the hashes this library has */
+    if (((uint32_t) hash_alg & 0x7f000000u) != 0x02000000u) return TLSREC_ERR_SSL_INTERNAL_ERROR;
+    *a = alg_index(hash_alg);
+    return *a < 0 ? TLSREC_ERR_SSL_BAD_INPUT_DATA : 0;
+}
+
+static int ladder_derive(int a, const unsigned char *secret, const char *label, const unsigned char *transcript,
+                         size_t transcript_len, unsigned char *dst)
+{
+    return derive_secret_impl(a, secret, alg_len(a), (const unsigned char *) label, strlen(label), transcript,
+                              transcript_len, TLSREC_TLS13_CONTEXT_HASHED, dst, alg_len(a));
+}
+
+extern "C" int tlsrec_tls13_derive_early_secrets(int hash_alg, const unsigned char *early_secret,
+                                                 const unsigned char *transcript, size_t transcript_len,
+                                                 tlsrec_tls13_early_secrets *derived)
+{
+    int a, r = ladder_alg(hash_alg, &a);
+    if (r) return r;
+    if (!early_secret || !derived || (!transcript && transcript_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    r = ladder_derive(a, early_secret, "c e traffic", transcript, transcript_len, derived->client_early_traffic_secret);
+    if (r == 0)
+        r = ladder_derive(a, early_secret, "e exp master", transcript, transcript_len,
+                          derived->early_exporter_master_secret);
+    return r;
+}
+
+extern "C" int tlsrec_tls13_derive_handshake_secrets(int hash_alg, const unsigned char *handshake_secret,
+                                                     const unsigned char *transcript, size_t transcript_len,
+                                                     tlsrec_tls13_handshake_secrets *derived)
+{
+    int a, r = ladder_alg(hash_alg, &a);
+    if (r) return r;
+    if (!handshake_secret || !derived || (!transcript && transcript_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    r = ladder_derive(a, handshake_secret, "c hs traffic", transcript, transcript_len,
+                      derived->client_handshake_traffic_secret);
+    if (r == 0)
+        r = ladder_derive(a, handshake_secret, "s hs traffic", transcript, transcript_len,
+                          derived->server_handshake_traffic_secret);
+    return r;
+}
+
+extern "C" int tlsrec_tls13_derive_application_secrets(int hash_alg, const unsigned char *application_secret,
+                                                       const unsigned char *transcript, size_t transcript_len,
+                                                       tlsrec_tls13_application_secrets *derived)
+{
+    int a, r = ladder_alg(hash_alg, &a);
+    if (r) return r;
+    if (!application_secret || !derived || (!transcript && transcript_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    r = ladder_derive(a, application_secret, "c ap traffic", transcript, transcript_len,
+                      derived->client_application_traffic_secret_N);
+    if (r == 0)
+        r = ladder_derive(a, application_secret, "s ap traffic", transcript, transcript_len,
+                          derived->server_application_traffic_secret_N);
+    if (r == 0)
+        r = ladder_derive(a, application_secret, "exp master", transcript, transcript_len,
+                          derived->exporter_master_secret);
+    return r;
+}
+
+extern "C" int tlsrec_tls13_derive_resumption_master_secret(int hash_alg, const unsigned char *application_secret,
+                                                            const unsigned char *transcript, size_t transcript_len,
+                                                            tlsrec_tls13_application_secrets *derived)
+{
+    int a, r = ladder_alg(hash_alg, &a);
+    if (r) return r;
+    if (!application_secret || !derived || (!transcript && transcript_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    return ladder_derive(a, application_secret, "res master", transcript, transcript_len,
+                         derived->resumption_master_secret);
+}
+
+/* ssl_tls13_calc_finished_core: EXPAND "finished" -> HMAC over the transcript hash, one job chain */
+static int calc_finished_impl(int a, const unsigned char *base, const unsigned char *transcript, unsigned char *dst)
+{
+    const size_t H = alg_len(a);
+    Arena ar;
+    uint8_t info[32];
+    const size_t il = encode_label(H, (const unsigned char *) "finished", 8, nullptr, 0, info);
+    const size_t o_base = ar.put(base, H), o_info = ar.put(info, il), o_tr = ar.put(transcript, H);
+    const size_t o_key = ar.put(nullptr, 64), o_out = ar.put(nullptr, 64);
+    Job j[2] = { job(OP_EXPAND, a, o_base, (uint32_t) H, o_info, (uint32_t) il, o_key, (uint32_t) H),
+                 job(OP_HMAC, a, o_key, (uint32_t) H, o_tr, (uint32_t) H, o_out, (uint32_t) H) };
+    const int first[3] = { 0, 1, 2 };
+    void *ho[1] = { dst };
+    return run_jobs(ar, j, first, 2, &o_out, ho, &H, 1);
+}
+
+extern "C" int tlsrec_tls13_calc_finished(int hash_alg, const unsigned char *base_secret,
+                                          const unsigned char *transcript, unsigned char *out, size_t *out_len)
+{
+    int a, r = ladder_alg(hash_alg, &a);
+    if (r) return r;
+    if (!base_secret || !transcript || !out || !out_len) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    r = calc_finished_impl(a, base_secret, transcript, out);
+    if (r == 0) *out_len = alg_len(a);
+    return r;
+}
+
+extern "C" int tlsrec_tls13_create_psk_binder(int hash_alg, const unsigned char *psk, size_t psk_len, int psk_type,
+                                              const unsigned char *transcript, unsigned char *result)
+{
+    int a, r = ladder_alg(hash_alg, &a);
+    if (r) return r;
+    if ((!psk && psk_len) || !transcript || !result) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    uint8_t early[64], binder_key[64];
+    r = tlsrec_tls13_evolve_secret(hash_alg, nullptr, psk, psk_len, early);
+    /* ssl_tls13_keys.c:879-895: "res binder" for a resumption PSK, "ext binder" for any other type */
+    const char *lbl = psk_type == TLSREC_TLS13_PSK_RESUMPTION ? "res binder" : "ext binder";
+    if (r == 0)
+        r = derive_secret_impl(a, early, alg_len(a), (const unsigned char *) lbl, 10, nullptr, 0,
+                               TLSREC_TLS13_CONTEXT_UNHASHED, binder_key, alg_len(a));
+    if (r == 0) r = calc_finished_impl(a, binder_key, transcript, result);
+    volatile uint8_t *v = early, *u = binder_key;
+    for (size_t i = 0; i < 64; i++) { v[i] = 0; u[i] = 0; }
+    return r;
+}
+
+/* ---- the ladder in batches (tls13_hs_kernel, tls13_app_kernel, tls13_mac_kernel) ---- */
+/* HMAC midstates of the zero salt, of Derive-Secret(Extract(0, 0), "derived", ""),
+ * and Hash(""): tests/tls13_ref.py ladder_constants() computes them from FIPS 180-4
+ * and hashlib, tests/test_tls13_ladder_cpu.py compares. */
+static const LadderConsts<L256> kConsts256 = {
+    { 0xf454deadu, 0x9725214fu, 0x90daf2a0u, 0xdf1228eau, 0x64e5750fu, 0xa3924181u, 0x824a932bu, 0xf8e04e32u },
+    { 0xd385480fu, 0x7abb6477u, 0x37c9c538u, 0x5dd82467u, 0x8e043a72u, 0x753434b0u, 0xdeb82818u, 0x361d45a6u },
+    { 0x8b35051cu, 0x8324ce6fu, 0xd35fd442u, 0x05006b0bu, 0x11f653deu, 0x87170024u, 0x53923a72u, 0x1a2e89f5u },
+    { 0x22b91d2fu, 0xa7f9ba55u, 0xba705a48u, 0xa6bef047u, 0xf5ba9b91u, 0xc425b796u, 0xdb8072a6u, 0x9037dbc2u },
+    { 0xe3b0c442u, 0x98fc1c14u, 0x9afbf4c8u, 0x996fb924u, 0x27ae41e4u, 0x649b934cu, 0xa495991bu, 0x7852b855u } };
+static const LadderConsts<L384> kConsts384 = {
+    { 0x53f869327560c3a2ULL, 0xc237b05164a5bbe8ULL, 0xe581f7394cfa66b8ULL, 0x846fa61922faad62ULL,
+      0xdd0b37ce462cff5eULL, 0x7ee8a4bdc87567f3ULL, 0x39bda99c75a047f7ULL, 0xc7bd628bd3f9a734ULL },
+    { 0xff6ce3f9ca86c81cULL, 0x585559c2ae0fc15cULL, 0xcf0d5686fb65a54eULL, 0xf1d54ee19e8cfd02ULL,
+      0xa5c720ab778ff100ULL, 0xdeb3e5f667573e8cULL, 0xc1bfc7ec16b591f3ULL, 0x34d487c1c79d59ebULL },
+    { 0x9540faa284271b10ULL, 0x940f9b21f2567a8cULL, 0x43d6380a7b89a867ULL, 0xedb7635f9865feb1ULL,
+      0x7c8b33059f3e823eULL, 0x9eb66f676065f021ULL, 0x79f7d919bede4e6dULL, 0x80ad994f8a39c726ULL },
+    { 0x9dcd6bc600f811e3ULL, 0xc556680dbba9586eULL, 0x987fb78efb62dcb7ULL, 0xb639835d0b42573aULL,
+      0x81cf02b2e173ad99ULL, 0x30a7f1029298d495ULL, 0x8aa72679937f7672ULL, 0xd31f72c4ad9a4b4cULL },
+    { 0x38b060a751ac9638ULL, 0x4cd9327eb1b1e36aULL, 0x21fdb71114be0743ULL, 0x4c0cc7bf63f6e1daULL,
+      0x274edebfe76f65fbULL, 0xd51ad2f14898b95bULL } };
+
+template <class T> static const LadderConsts<T> &ladder_consts();
+template <> const LadderConsts<L256> &ladder_consts<L256>() { return kConsts256; }
+template <> const LadderConsts<L384> &ladder_consts<L384>() { return kConsts384; }
+
+/* Host-only: the constants of `hash_alg` widened to 64 bits, zero_ip | zero_op |
+ * d0_ip | d0_op | empty (40 words for SHA-256, 38 for SHA-384); returns the count. */
+extern "C" int tlsrec__tls13_ladder_consts(int hash_alg, uint64_t *out)
+{
+    const int a = alg_index(hash_alg);
+    if (a < 0 || !out) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    int n = 0;
+    if (a == H_SHA384) {
+        const LadderConsts<L384> &k = kConsts384;
+        for (int j = 0; j < 8; j++) out[n++] = k.zero_ip[j];
+        for (int j = 0; j < 8; j++) out[n++] = k.zero_op[j];
+        for (int j = 0; j < 8; j++) out[n++] = k.d0_ip[j];
+        for (int j = 0; j < 8; j++) out[n++] = k.d0_op[j];
+        for (int j = 0; j < L384::HW; j++) out[n++] = k.empty[j];
+    } else {
+        const LadderConsts<L256> &k = kConsts256;
+        for (int j = 0; j < 8; j++) out[n++] = k.zero_ip[j];
+        for (int j = 0; j < 8; j++) out[n++] = k.zero_op[j];
+        for (int j = 0; j < 8; j++) out[n++] = k.d0_ip[j];
+        for (int j = 0; j < 8; j++) out[n++] = k.d0_op[j];
+        for (int j = 0; j < L256::HW; j++) out[n++] = k.empty[j];
+    }
+    return n;
+}
+
+/* HkdfLabel(desired, label, context of ctx_len bytes to follow) as the kernels' cells */
+static LabelW label_cells(size_t desired, const void *label, size_t label_len, size_t ctx_len)
+{
+    uint8_t b[24] = { 0 };
+    encode_label(desired, (const unsigned char *) label, label_len, nullptr, ctx_len, b);
+    LabelW l;
+    for (int c = 0; c < 6; c++)
+        l.c[c] = ((uint32_t) b[4 * c] << 24) | ((uint32_t) b[4 * c + 1] << 16) | ((uint32_t) b[4 * c + 2] << 8) | b[4 * c + 3];
+    return l;
+}
+
+static LadderLabels ladder_labels(size_t H, size_t key_len, const char *c_traffic, const char *s_traffic,
+                                  const char *extra)
+{
+    LadderLabels lb;
+    lb.derived = label_cells(H, "derived", 7, H);
+    lb.c_traffic = label_cells(H, c_traffic, 12, H);
+    lb.s_traffic = label_cells(H, s_traffic, 12, H);
+    lb.extra = label_cells(H, extra, strlen(extra), H);
+    lb.key = label_cells(key_len, "key", 3, 0);
+    lb.iv = label_cells(12, "iv", 2, 0);
+    lb.fin = label_cells(H, "finished", 8, 0);
+    return lb;
+}
+
+static inline uint32_t al(const void *p, uint32_t bit) { return ((uintptr_t) p & 15) == 0 ? bit : 0u; }
+
+/* the checks the two stages share, in the header's order; *alg: the suite's hash as in tlsrec_tls13_keytab_derive */
+static int ladder_check(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, bool null_array, uint32_t psk_len,
+                        uint32_t shared_len, int *alg)
+{
+    if (!kt || (null_array && count) || psk_len > 48) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const uint32_t cap = tlsrec_keytab_capacity(kt);
+    if (first > cap || (uint64_t) count * 2 > (uint64_t) (cap - first)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (tlsrec_cipher_keylen(cipher) == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (shared_len != 0 && shared_len != 32 && shared_len != 48 && shared_len != 56 && shared_len != 66)
+        return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    *alg = cipher == TLSREC_CIPHER_AES_256_GCM ? H_SHA384 : H_SHA256;
+    return 0;
+}
+
+static uint32_t tls13_head(int cipher)
+{
+    /* tlsrec_key_material: cipher, tls_minor 4, fixed_ivlen 12 (ssl_tls13_keys.c:985-998), taglen */
+    return (uint32_t) cipher | (4u << 8) | (12u << 16) | ((uint32_t) tlsrec_cipher_taglen(cipher) << 24);
+}
+
+template <class T>
+static hipError_t hs_launch(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, uint32_t psk_len,
+                            uint32_t shared_len, const tlsrec_tls13_hs_conn *conns, tlsrec_tls13_secret *hs_traffic,
+                            tlsrec_tls13_secret *finished_keys, tlsrec_tls13_secret *master, hipStream_t st)
+{
+    Tls13HsArgs<T> a;
+    a.conns = conns;
+    a.out = tlsrec__keytab_stage(kt) + first;
+    a.hs_traffic = hs_traffic;
+    a.finished = finished_keys;
+    a.master = master;
+    a.count = count;
+    a.head = tls13_head(cipher);
+    a.key_cells = tlsrec_cipher_keylen(cipher) / 4;
+    a.psk_len = psk_len;
+    a.shared_len = shared_len;
+    a.aligned = al(conns, AL_CONNS) | al(hs_traffic, AL_TRAFFIC) | al(finished_keys, AL_AUX) | al(master, AL_MASTER);
+    a.k = ladder_consts<T>();
+    a.lb = ladder_labels(T::HB, tlsrec_cipher_keylen(cipher), "c hs traffic", "s hs traffic", "");
+    hipLaunchKernelGGL(tls13_hs_kernel<T>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+/* The derive kernel alone (see tlsrec__tls13_stage_keys). */
+extern "C" int tlsrec__tls13_stage_hs_keys(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                           uint32_t psk_len, uint32_t shared_len, const tlsrec_tls13_hs_conn *conns,
+                                           tlsrec_tls13_secret *hs_traffic, tlsrec_tls13_secret *finished_keys,
+                                           tlsrec_tls13_secret *master, void *stream)
+{
+    int alg;
+    int r = ladder_check(kt, first, count, cipher, !conns || !hs_traffic || !master, psk_len, shared_len, &alg);
+    if (r != 0 || count == 0) return r;
+    hipStream_t st = (hipStream_t) stream;
+    const hipError_t e = alg == H_SHA384
+        ? hs_launch<L384>(kt, first, count, cipher, psk_len, shared_len, conns, hs_traffic, finished_keys, master, st)
+        : hs_launch<L256>(kt, first, count, cipher, psk_len, shared_len, conns, hs_traffic, finished_keys, master, st);
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls13_keytab_derive_handshake(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                                    uint32_t psk_len, uint32_t shared_len,
+                                                    const tlsrec_tls13_hs_conn *conns, tlsrec_tls13_secret *hs_traffic,
+                                                    tlsrec_tls13_secret *finished_keys, tlsrec_tls13_secret *master,
+                                                    void *stream)
+{
+    int r = tlsrec__tls13_stage_hs_keys(kt, first, count, cipher, psk_len, shared_len, conns, hs_traffic, finished_keys,
+                                        master, stream);
+    if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, 2 * count, cipher, (hipStream_t) stream);
+    return r;
+}
+
+template <class T>
+static hipError_t app_launch(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                             const tlsrec_tls13_secret *master, const tlsrec_tls13_secret *transcripts,
+                             tlsrec_tls13_secret *app_traffic, tlsrec_tls13_secret *exporter, hipStream_t st)
+{
+    Tls13AppArgs<T> a;
+    a.master = master;
+    a.transcripts = transcripts;
+    a.out = tlsrec__keytab_stage(kt) + first;
+    a.app_traffic = app_traffic;
+    a.exporter = exporter;
+    a.count = count;
+    a.head = tls13_head(cipher);
+    a.key_cells = tlsrec_cipher_keylen(cipher) / 4;
+    a.aligned = al(master, AL_MASTER) | al(transcripts, AL_TRANSCRIPT) | al(app_traffic, AL_TRAFFIC) | al(exporter, AL_AUX);
+    a.lb = ladder_labels(T::HB, tlsrec_cipher_keylen(cipher), "c ap traffic", "s ap traffic", "exp master");
+    hipLaunchKernelGGL(tls13_app_kernel<T>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+extern "C" int tlsrec__tls13_stage_app_keys(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                            const tlsrec_tls13_secret *master, const tlsrec_tls13_secret *transcripts,
+                                            tlsrec_tls13_secret *app_traffic, tlsrec_tls13_secret *exporter, void *stream)
+{
+    int alg;
+    int r = ladder_check(kt, first, count, cipher, !master || !transcripts || !app_traffic, 0, 0, &alg);
+    if (r != 0 || count == 0) return r;
+    hipStream_t st = (hipStream_t) stream;
+    const hipError_t e = alg == H_SHA384
+        ? app_launch<L384>(kt, first, count, cipher, master, transcripts, app_traffic, exporter, st)
+        : app_launch<L256>(kt, first, count, cipher, master, transcripts, app_traffic, exporter, st);
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls13_keytab_derive_application(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                                      const tlsrec_tls13_secret *master,
+                                                      const tlsrec_tls13_secret *transcripts,
+                                                      tlsrec_tls13_secret *app_traffic, tlsrec_tls13_secret *exporter,
+                                                      void *stream)
+{
+    int r = tlsrec__tls13_stage_app_keys(kt, first, count, cipher, master, transcripts, app_traffic, exporter, stream);
+    if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, 2 * count, cipher, (hipStream_t) stream);
+    return r;
+}
+
+static int mac_launch(int hash_alg, uint32_t label_len, const unsigned char *label, const tlsrec_tls13_secret *keys,
+                      const tlsrec_tls13_secret *msgs, tlsrec_tls13_secret *out, uint32_t count, void *stream)
+{
+    const int alg = alg_index(hash_alg);
+    if (alg < 0) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if ((!keys || !msgs || !out) && count) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (count == 0) return 0;
+    static const int device = tlsrec_device_check();     /* no key table vouches for a device here; asked once */
+    if (device != 0) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    Tls13MacArgs a;
+    a.keys = keys;
+    a.msgs = msgs;
+    a.out = out;
+    a.count = count;
+    a.aligned = al(keys, AL_MASTER) | al(msgs, AL_TRANSCRIPT) | al(out, AL_AUX);
+    a.label_len = label_len;
+    memset(&a.label, 0, sizeof(a.label));
+    if (label_len != MAC_PLAIN) a.label = label_cells(alg_len(alg), label, label_len, alg_len(alg));
+    hipStream_t st = (hipStream_t) stream;
+    if (alg == H_SHA384) hipLaunchKernelGGL(tls13_mac_kernel<L384>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(tls13_mac_kernel<L256>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls13_batch_verify_data(int hash_alg, const tlsrec_tls13_secret *finished_keys,
+                                              const tlsrec_tls13_secret *transcripts, tlsrec_tls13_secret *out,
+                                              uint32_t count, void *stream)
+{
+    return mac_launch(hash_alg, MAC_PLAIN, nullptr, finished_keys, transcripts, out, count, stream);
+}
+
+extern "C" int tlsrec_tls13_batch_derive_secret(int hash_alg, const unsigned char *label, size_t label_len,
+                                                const tlsrec_tls13_secret *secrets, const tlsrec_tls13_secret *transcripts,
+                                                tlsrec_tls13_secret *out, uint32_t count, void *stream)
+{
+    if (label_len > 12 || (!label && label_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    return mac_launch(hash_alg, (uint32_t) label_len, label, secrets, transcripts, out, count, stream);
 }
 
 /* ======================================================================

@@ -88,3 +88,102 @@ def keytab_derive(kt: KeyTable, first: int, count: int, cipher: int, secrets, ke
     (tlsrec_tls13_secret); updated in place when key_update."""
     _chk("tlsrec_tls13_keytab_derive", _abi.load().tlsrec_tls13_keytab_derive(
         kt.handle, first, count, cipher, _ptr(secrets), int(bool(key_update)), _stream(stream)))
+
+
+# ---- the rest of the ladder (RFC 8446 7.1) ---------------------------------------
+#    mbedtls_ssl_tls13_derive_early_secrets            (:421) -> derive_early_secrets
+#    mbedtls_ssl_tls13_derive_handshake_secrets        (:479) -> derive_handshake_secrets
+#    mbedtls_ssl_tls13_derive_application_secrets      (:545) -> derive_application_secrets
+#    mbedtls_ssl_tls13_derive_resumption_master_secret (:621) -> derive_resumption_master_secret
+#    ssl_tls13_calc_finished_core                      (:697) -> calc_finished
+#    mbedtls_ssl_tls13_create_psk_binder               (:832) -> create_psk_binder
+#    batches: keytab_derive_handshake, keytab_derive_application, batch_verify_data, batch_derive_secret
+PSK_EXTERNAL = _abi.TLS13_PSK_EXTERNAL
+PSK_RESUMPTION = _abi.TLS13_PSK_RESUMPTION
+SECRET_BYTES = ctypes.sizeof(_abi.CTls13Secret)      # 48
+HS_CONN_BYTES = ctypes.sizeof(_abi.CTls13HsConn)     # 176: psk[48] || shared[80] || transcript[48]
+
+
+def _helper(name, struct, fields, hash_alg, secret, transcript):
+    out = struct()
+    _chk(name, getattr(_abi.load(), name)(hash_alg, _b(secret), _b(transcript), len(transcript), ctypes.byref(out)))
+    n = HASH_LEN[hash_alg]
+    return tuple(bytes(getattr(out, f)[:n]) for f in fields)
+
+
+def derive_early_secrets(hash_alg: int, early_secret: bytes, transcript: bytes):
+    """(client_early_traffic_secret, early_exporter_master_secret)"""
+    return _helper("tlsrec_tls13_derive_early_secrets", _abi.CTls13EarlySecrets,
+                   ("client_early_traffic_secret", "early_exporter_master_secret"), hash_alg, early_secret, transcript)
+
+
+def derive_handshake_secrets(hash_alg: int, handshake_secret: bytes, transcript: bytes):
+    """(client_handshake_traffic_secret, server_handshake_traffic_secret)"""
+    return _helper("tlsrec_tls13_derive_handshake_secrets", _abi.CTls13HandshakeSecrets,
+                   ("client_handshake_traffic_secret", "server_handshake_traffic_secret"), hash_alg,
+                   handshake_secret, transcript)
+
+
+def derive_application_secrets(hash_alg: int, master_secret: bytes, transcript: bytes):
+    """(client_application_traffic_secret_0, server_application_traffic_secret_0, exporter_master_secret)"""
+    return _helper("tlsrec_tls13_derive_application_secrets", _abi.CTls13ApplicationSecrets,
+                   ("client_application_traffic_secret_N", "server_application_traffic_secret_N",
+                    "exporter_master_secret"), hash_alg, master_secret, transcript)
+
+
+def derive_resumption_master_secret(hash_alg: int, master_secret: bytes, transcript: bytes) -> bytes:
+    return _helper("tlsrec_tls13_derive_resumption_master_secret", _abi.CTls13ApplicationSecrets,
+                   ("resumption_master_secret",), hash_alg, master_secret, transcript)[0]
+
+
+def calc_finished(hash_alg: int, base_secret: bytes, transcript: bytes) -> bytes:
+    """verify_data of a Finished message under `base_secret` (a handshake traffic secret)"""
+    out, n = ctypes.create_string_buffer(64), ctypes.c_size_t(0)
+    _chk("tlsrec_tls13_calc_finished", _abi.load().tlsrec_tls13_calc_finished(
+        hash_alg, _b(base_secret), _b(transcript), out, ctypes.byref(n)))
+    return out.raw[:n.value]
+
+
+def create_psk_binder(hash_alg: int, psk: bytes, psk_type: int, transcript: bytes) -> bytes:
+    out = ctypes.create_string_buffer(64)
+    _chk("tlsrec_tls13_create_psk_binder", _abi.load().tlsrec_tls13_create_psk_binder(
+        hash_alg, _b(psk), len(psk), psk_type, _b(transcript), out))
+    return out.raw[:HASH_LEN[hash_alg]]
+
+
+def _h(kt):
+    return kt.handle if kt is not None else None
+
+
+def keytab_derive_handshake(kt: KeyTable, first: int, count: int, cipher: int, psk_len: int, shared_len: int, conns,
+                            hs_traffic, finished_keys, master, stream=None) -> None:
+    """`conns`: device buffer of count x 176 bytes (tlsrec_tls13_hs_conn), only
+    read.  Outputs, device buffers of 48-byte elements: hs_traffic and
+    finished_keys (or None) 2 x count in slot order, master count.  Connection
+    i's client_write keys land in slot first + 2*i, server_write in first + 2*i + 1
+    (mbedtls_amd.tls12.tls12_slots gives an endpoint's pair)."""
+    _chk("tlsrec_tls13_keytab_derive_handshake", _abi.load().tlsrec_tls13_keytab_derive_handshake(
+        _h(kt), first, count, cipher, psk_len, shared_len, _ptr(conns), _ptr(hs_traffic), _ptr(finished_keys),
+        _ptr(master), _stream(stream)))
+
+
+def keytab_derive_application(kt: KeyTable, first: int, count: int, cipher: int, master, transcripts, app_traffic,
+                              exporter, stream=None) -> None:
+    """`master`, `transcripts` (Hash(ClientHello..server Finished)): count x 48
+    bytes on the device; app_traffic 2 x count in slot order (what keytab_derive
+    takes for a KeyUpdate), exporter count or None."""
+    _chk("tlsrec_tls13_keytab_derive_application", _abi.load().tlsrec_tls13_keytab_derive_application(
+        _h(kt), first, count, cipher, _ptr(master), _ptr(transcripts), _ptr(app_traffic), _ptr(exporter),
+        _stream(stream)))
+
+
+def batch_verify_data(hash_alg: int, finished_keys, transcripts, out, count: int, stream=None) -> None:
+    """out[i] = HMAC(finished_keys[i], transcripts[i]); device buffers of 48-byte elements"""
+    _chk("tlsrec_tls13_batch_verify_data", _abi.load().tlsrec_tls13_batch_verify_data(
+        hash_alg, _ptr(finished_keys), _ptr(transcripts), _ptr(out), count, _stream(stream)))
+
+
+def batch_derive_secret(hash_alg: int, label: bytes, secrets, transcripts, out, count: int, stream=None) -> None:
+    """out[i] = Derive-Secret(secrets[i], label, hashed context transcripts[i]); label of at most 12 bytes"""
+    _chk("tlsrec_tls13_batch_derive_secret", _abi.load().tlsrec_tls13_batch_derive_secret(
+        hash_alg, _b(label), len(label), _ptr(secrets), _ptr(transcripts), _ptr(out), count, _stream(stream)))

@@ -22,12 +22,20 @@ on a sample of at most 2 048 connections, and (d) tlsrec_tls12_keytab_derive
 for AES-128-GCM over the same connections as the yardstick, and states the
 derive kernels' cost per SHA-2 compression (DESIGN 3.5's 5n + 3 / 5n + 2).
 
+--tls13-handshake: the TLS 1.3 ladder (tlsrec_tls13_keytab_derive_handshake,
+_application, tlsrec_tls13_batch_verify_data, _batch_derive_secret) over 64 K
+connections of one (cipher, psk_len, shared_len): each call, each stage's
+derive kernel alone, the single-shot ladder + tlsrec_keytab_load it replaces
+on at most 2 048 connections, and the tlsrec_tls12_keytab_derive AES-128-GCM
+kernel under the same hash for a ns-per-compression yardstick.
+
 Prints one JSON line; the whole call and the derive kernel alone are timed
 with HIP events on the call's stream, the key-setup kernel is the difference.
 
     python tools/bench_keysched.py [--count 65536] [--cipher 2] [--steps 5]
     python tools/bench_keysched.py --tls12 [--prf sha256|sha384] [--count 65536] [--cipher 1]
     python tools/bench_keysched.py --tls12 --cbc-mac 2 [--etm] [--count 65536]
+    python tools/bench_keysched.py --tls13-handshake [--cipher 1|2] [--psk-len 32] [--shared-len 32]
 """
 import argparse
 import ctypes
@@ -276,8 +284,160 @@ def main_tls12_cbc(a):
                                     "builds are not counted", "tls12 cbc derive + cbc key setup + staging wipe")}))
 
 
+def host_tls13_ladder_leg(hash_alg, cipher, psk_len, shared_len, raw, traw, sample):
+    """The path without the batch, for `sample` connections: the single-shot
+    ladder per connection (a synchronised job chain per step, every secret back
+    on the host), then one tlsrec_keytab_load per stage."""
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import keysched as K
+    H, kl = K.HASH_LEN[hash_alg], M.KEYLEN[cipher]
+    kt = M.KeyTable(2 * sample)
+    K.evolve_secret(hash_alg, None, None)                        # the control-path stream and arena exist
+
+    def load(pairs):
+        km = np.concatenate([M.key_material(cipher, M.VERSION_TLS1_3, k, iv) for k, iv in pairs])
+        t0 = time.perf_counter()
+        kt.load(km)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pairs, masters = [], []
+    for i in range(sample):
+        c = raw[176 * i:176 * i + 176]
+        early = K.evolve_secret(hash_alg, None, c[:psk_len] or None)
+        hs = K.evolve_secret(hash_alg, early, c[48:48 + shared_len] or None)
+        cs, ss = K.derive_handshake_secrets(hash_alg, hs, c[128:128 + H])
+        ck, civ, sk, siv = K.make_traffic_keys(hash_alg, cs, ss, kl, 12)
+        for s in (cs, ss):
+            K.hkdf_expand_label(hash_alg, s, b"finished", b"", H)
+        masters.append(K.evolve_secret(hash_alg, hs, None))
+        pairs += [(ck, civ), (sk, siv)]
+    hs_s = time.perf_counter() - t0
+    hs_load = load(pairs)
+    t0 = time.perf_counter()
+    pairs = []
+    for i in range(sample):
+        ca, sa, _ = K.derive_application_secrets(hash_alg, masters[i], traw[48 * i:48 * i + H])
+        ck, civ, sk, siv = K.make_traffic_keys(hash_alg, ca, sa, kl, 12)
+        pairs += [(ck, civ), (sk, siv)]
+    app_s = time.perf_counter() - t0
+    app_load = load(pairs)
+    kt.close()
+
+    def row(ladder, ld):
+        return {"value": round(sample / (ladder + ld)), "unit": "connections/s",
+                "us_per_connection": round((ladder + ld) / sample * 1e6, 2), "ladder_seconds": round(ladder, 4),
+                "keytab_load_seconds": round(ld, 4)}
+    return {"sample_connections": sample, "handshake": row(hs_s, hs_load), "application": row(app_s, app_load),
+            "what": "per connection the single-shot calls (handshake: evolve_secret x3, derive_handshake_secrets, "
+                    "make_traffic_keys, hkdf_expand_label \"finished\" x2; application: derive_application_secrets, "
+                    "make_traffic_keys), then one tlsrec_keytab_load of the stage's records; wall time"}
+
+
+def main_tls13_handshake(a):
+    """tlsrec_tls13_keytab_derive_handshake / _application and the two table-less
+    batches: each call, each stage's derive kernel alone, the host path they
+    replace, and the TLS 1.2 AES-128-GCM derive kernel of the same run under
+    the same hash as the ns-per-compression yardstick."""
+    from tools import rowlib
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import keysched as K
+    from mbedtls_amd import tls12 as T
+    from mbedtls_amd.batch import _ptr, _stream
+    from tests.prng import prng_array
+    dev = torch.device("cuda")
+    L = M.load()
+    vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+    L.tlsrec__tls13_stage_hs_keys.restype = ci
+    L.tlsrec__tls13_stage_hs_keys.argtypes = [vp, u32, u32, ci, u32, u32, vp, vp, vp, vp, vp]
+    L.tlsrec__tls13_stage_app_keys.restype = ci
+    L.tlsrec__tls13_stage_app_keys.argtypes = [vp, u32, u32, ci, vp, vp, vp, vp, vp]
+    L.tlsrec__tls12_stage_keys.restype = ci
+    L.tlsrec__tls12_stage_keys.argtypes = [vp, u32, u32, ci, ci, vp, vp]
+    cipher, pl, sl, n = a.cipher, a.psk_len, a.shared_len, a.count
+    sha384 = cipher == M.CIPHER_AES_256_GCM
+    hname, alg = ("sha384", K.ALG_SHA_384) if sha384 else ("sha256", K.ALG_SHA_256)
+    raw, traw = prng_array(0x7153, n * 176), prng_array(0x7154, n * 48)
+    conns, trs = torch.from_numpy(raw).to(dev), torch.from_numpy(traw).to(dev)
+    conns12 = torch.from_numpy(prng_array(0x7152, n * 112)).to(dev)
+
+    def buf(k):
+        return torch.zeros(k * 48, dtype=torch.uint8, device=dev)
+
+    hs, fin, ms, app, exp, vd, rm = buf(2 * n), buf(2 * n), buf(n), buf(2 * n), buf(n), buf(2 * n), buf(n)
+    kt, kt12 = M.KeyTable(2 * n), M.KeyTable(2 * n)
+    prf12 = T.PRF_SHA384 if sha384 else T.PRF_SHA256
+
+    def ok(r):
+        assert r == 0, r
+
+    s = _stream(None)
+    legs = {
+        "hs_call": lambda: K.keytab_derive_handshake(kt, 0, n, cipher, pl, sl, conns, hs, fin, ms),
+        "hs_derive_kernel": lambda: ok(L.tlsrec__tls13_stage_hs_keys(kt.handle, 0, n, cipher, pl, sl, _ptr(conns), _ptr(hs),
+                                                                      _ptr(fin), _ptr(ms), s)),
+        "app_call": lambda: K.keytab_derive_application(kt, 0, n, cipher, ms, trs, app, exp),
+        "app_derive_kernel": lambda: ok(L.tlsrec__tls13_stage_app_keys(kt.handle, 0, n, cipher, _ptr(ms), _ptr(trs),
+                                                                        _ptr(app), _ptr(exp), s)),
+        "verify_data": lambda: K.batch_verify_data(alg, fin, hs, vd, 2 * n),
+        "derive_secret": lambda: K.batch_derive_secret(alg, b"res master", ms, trs, rm, n),
+        "tls12_derive_kernel": lambda: ok(L.tlsrec__tls12_stage_keys(kt12.handle, 0, n, M.CIPHER_AES_128_GCM, prf12,
+                                                                     _ptr(conns12), s)),
+    }
+    ms_, wall = {}, {}
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()
+        ms_[name], wall[name] = rowlib.event_timed(fn, a.steps)
+    legs["app_call"]()          # (the kernel-alone legs staged keys the table never took)
+    torch.cuda.synchronize()
+    comp = {"hs": (8 if pl else 0) + (3 if not sha384 and sl > 55 else 2) + 2 + 4 + 6 + 16, "app": 20,
+            "verify_data": 4, "derive_secret": 4, "tls12": _compressions(hname, 40)}
+    per = {"hs": n, "app": n, "verify_data": 2 * n, "derive_secret": n, "tls12": n}
+    leg = {"hs": "hs_derive_kernel", "app": "app_derive_kernel", "verify_data": "verify_data",
+           "derive_secret": "derive_secret", "tls12": "tls12_derive_kernel"}
+    ns = {k: ms_[leg[k]] * 1e6 / per[k] / comp[k] for k in comp}
+    host = None if a.no_cpu else host_tls13_ladder_leg(alg, cipher, pl, sl, raw.tobytes(), traw.tobytes(), min(2048, n))
+    cps = {k: n / (ms_[k + "_call"] / 1e3) for k in ("hs", "app")}
+
+    def stage(k):
+        return {"connections_per_s": round(cps[k]), "ms_per_batch_events": round(ms_[k + "_call"], 4),
+                "ms_per_batch_wall": round(wall[k + "_call"] * 1e3, 4),
+                "derive_kernel_ms": round(ms_[k + "_derive_kernel"], 4),
+                "key_setup_ms": round(ms_[k + "_call"] - ms_[k + "_derive_kernel"], 4),
+                "compressions_per_connection": comp[k],
+                "derive_kernel_ns_per_compression": round(ns[k], 4),
+                "per_compression_vs_tls12_kernel_same_hash": round(ns[k] / ns["tls12"], 3),
+                "speedup_vs_host_path": round(cps[k] / host["handshake" if k == "hs" else "application"]["value"], 1)
+                if host else None}
+    print(json.dumps({
+        "metric": "TLS 1.3 handshake-stage key derivations into the key table per second", "value": round(cps["hs"]),
+        "unit": "connections/s", "count": n, "slots": 2 * n, "cipher": cipher, "hash": hname, "psk_len": pl,
+        "shared_len": sl, "handshake_stage": stage("hs"), "application_stage": stage("app"),
+        "batch_verify_data": {"count": 2 * n, "ms": round(ms_["verify_data"], 4),
+                              "ns_per_compression": round(ns["verify_data"], 4)},
+        "batch_derive_secret": {"count": n, "label": "res master", "ms": round(ms_["derive_secret"], 4),
+                                "ns_per_compression": round(ns["derive_secret"], 4)},
+        "tls12_aes128gcm_same_run": {"prf": hname, "derive_kernel_ms": round(ms_["tls12_derive_kernel"], 4),
+                                     "compressions_per_connection": comp["tls12"],
+                                     "derive_kernel_ns_per_compression": round(ns["tls12"], 4)},
+        "host_path": host,
+        "roofline": rowlib.roofline((176 + 5 * 48 + 128) * n, ms_["hs_call"], "per connection: the 176-byte "
+                                    "tlsrec_tls13_hs_conn read, five 48-byte secrets and two 64-byte key records "
+                                    "written; the key-table slots the key setup builds are not counted",
+                                    "tls13 handshake stage + key setup")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tls13-handshake", action="store_true",
+                    help="the TLS 1.3 ladder batches (tlsrec_tls13_keytab_derive_handshake / _application)")
+    ap.add_argument("--psk-len", type=int, default=32, help="--tls13-handshake: 0..48")
+    ap.add_argument("--shared-len", type=int, default=32, help="--tls13-handshake: 0, 32, 48, 56 or 66")
     ap.add_argument("--count", type=int, default=65536)
     ap.add_argument("--cipher", type=int, default=None, help="default 2 (with --cbc-mac: the suite's, 23 or 24)")
     ap.add_argument("--steps", type=int, default=5)
@@ -291,6 +451,9 @@ def main():
                     help="--tls12: an AES-CBC + HMAC suite (1 SHA-1, 2 SHA-256, 3 SHA-384), tlsrec_tls12_keytab_derive_cbc")
     ap.add_argument("--etm", action="store_true", help="--cbc-mac: encrypt-then-MAC slots")
     a = ap.parse_args()
+    if a.tls13_handshake:
+        a.cipher = 1 if a.cipher is None else a.cipher
+        return main_tls13_handshake(a)
     if a.cbc_mac:
         if not a.tls12:
             ap.error("--cbc-mac goes with --tls12")

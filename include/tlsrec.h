@@ -540,6 +540,76 @@ int tlsrec_tls13_batch_derive_secret(int hash_alg, const unsigned char *label, s
                                      const tlsrec_tls13_secret *secrets, const tlsrec_tls13_secret *transcripts,
                                      tlsrec_tls13_secret *out, uint32_t count, void *stream);
 
+/* One offered PSK at its ClientHello: 144 bytes, device-resident, only read */
+typedef struct tlsrec_tls13_psk_conn {
+    uint8_t psk[48];                /* psk_len bytes used */
+    uint8_t binder_transcript[48];  /* Hash(truncated ClientHello), Hash.length bytes used */
+    uint8_t hello_transcript[48];   /* Hash(ClientHello); read only by tlsrec_tls13_keytab_derive_early */
+} tlsrec_tls13_psk_conn;
+
+/* Batch, PSK binder: what a server does once per resumed ClientHello,
+ * ssl_tls13_offered_psks_check_binder_match (ssl_tls13_server.c:404-457) over
+ * mbedtls_ssl_tls13_create_psk_binder (ssl_tls13_keys.c:832-917).  For each of `count`
+ * connections, in one kernel:
+ *   Early Secret = Extract(0, PSK)
+ *   binder_key = Derive-Secret(., "res binder" | "ext binder", "")   (psk_type as in
+ *                                             tlsrec_tls13_create_psk_binder: "res binder" for
+ *                                             TLSREC_TLS13_PSK_RESUMPTION, "ext binder" otherwise)
+ *   binder = the Finished MAC of binder_key over binder_transcript   -> binders[i] (may be NULL)
+ *   match[i] = 1 if the first Hash.length bytes of offered[i] equal the binder, else 0
+ * The compare ORs the XOR of every cell, with no early exit and no branch on the data, as
+ * mbedtls_ct_memcmp does; bytes of offered[i] past Hash.length are not looked at.  offered
+ * and match are both given or both NULL (a client computing its own binders passes NULL,
+ * NULL); binders may be NULL only when match is given.  psk_len (1..48) and psk_type hold
+ * for the whole call.  Every array is a device array; a 48-byte output element holds
+ * Hash.length value bytes, the rest is written as zero; match is one uint32_t per
+ * connection.  Asynchronous on `stream`, no host round trip; the inputs must stay valid
+ * until the stream reaches the call.
+ * Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for a hash other than SHA-256 /
+ * SHA-384, for conns NULL with count != 0, for only one of offered and match given, for
+ * binders and match both NULL with count != 0, for psk_len == 0 or psk_len > 48.
+ * count == 0 then returns 0. */
+int tlsrec_tls13_batch_psk_binder(int hash_alg, uint32_t psk_len, int psk_type,
+                                  const tlsrec_tls13_psk_conn *conns, const tlsrec_tls13_secret *offered,
+                                  tlsrec_tls13_secret *binders, uint32_t *match, uint32_t count, void *stream);
+
+/* Batch, early stage: tlsrec_tls13_batch_psk_binder and, in the same kernel pass,
+ * ssl_tls13_generate_early_key (ssl_tls13_keys.c:1086-1182) with
+ * mbedtls_ssl_tls13_compute_early_transform (:1184-1225):
+ *   c e traffic over hello_transcript                 -> early_traffic[i]
+ *   e exp master over hello_transcript                -> early_exporter[i] (may be NULL: not computed)
+ *   the key / iv of c e traffic                       -> slot first + i
+ * One slot per connection, the client_write direction: a client writes 0-RTT records
+ * with it, a server reads them.  The slots are loaded as TLS 1.3 keys of `cipher`
+ * (tls_minor 4, fixed_ivlen 12); the hash follows the cipher as in
+ * tlsrec_tls13_keytab_derive_handshake.  The slot is loaded whether or not the binder
+ * matched: match[i] == 0 means the caller drops the connection and MUST NOT use slot
+ * first + i, whose key then belongs to a PSK the peer has not proved it holds.
+ * Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for kt NULL, for conns or
+ * early_traffic NULL with count != 0, for the offered / match / binders rule and the
+ * psk_len range of tlsrec_tls13_batch_psk_binder, for [first, first + count) overflowing
+ * or running past the table; TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for an unknown cipher.
+ * count == 0 then returns 0. */
+int tlsrec_tls13_keytab_derive_early(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                     uint32_t psk_len, int psk_type, const tlsrec_tls13_psk_conn *conns,
+                                     const tlsrec_tls13_secret *offered, tlsrec_tls13_secret *binders, uint32_t *match,
+                                     tlsrec_tls13_secret *early_traffic, tlsrec_tls13_secret *early_exporter,
+                                     void *stream);
+
+/* Batch, ticket PSK (RFC 8446 4.6.1; ssl_tls13_server.c:3219-3230, ssl_tls13_client.c:2975-2990):
+ *   psk[i] = HKDF-Expand-Label(res_master[i], "resumption", nonces[32 i .. 32 i + nonce_len), Hash.length)
+ * between tlsrec_tls13_batch_derive_secret("res master") and tlsrec_ticket_write.  nonces
+ * holds 32 bytes per ticket (MBEDTLS_SSL_TLS1_3_TICKET_NONCE_LENGTH), of which the first
+ * nonce_len (0..32, the same for the whole call) are the nonce; the rest is not looked at.
+ * The one divergence: a nonce longer than 32 bytes is TLSREC_ERR_SSL_FEATURE_UNAVAILABLE
+ * here and stays with tlsrec_tls13_hkdf_expand_label.
+ * Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for a hash other than SHA-256 /
+ * SHA-384, for a NULL array with count != 0; TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for
+ * nonce_len > 32.  count == 0 then returns 0. */
+int tlsrec_tls13_batch_ticket_psk(int hash_alg, uint32_t nonce_len, const tlsrec_tls13_secret *res_master,
+                                  const uint8_t *nonces /* count x 32 bytes */, tlsrec_tls13_secret *psk,
+                                  uint32_t count, void *stream);
+
 /* ---- TLS 1.2 / DTLS 1.2 key derivation (library/ssl_tls.c) ---------------
  * The TLS 1.2 PRF (RFC 5246 section 5, P_SHA256 / P_SHA384) on the GPU: the
  * reference's single-shot functions, and a batch that expands many

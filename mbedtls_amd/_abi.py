@@ -151,6 +151,12 @@ class CTls13HsConn(ctypes.Structure):
     _fields_ = [("psk", ctypes.c_ubyte * 48), ("shared", ctypes.c_ubyte * 80), ("transcript", ctypes.c_ubyte * 48)]
 
 
+class CTls13PskConn(ctypes.Structure):
+    """tlsrec_tls13_psk_conn: one offered PSK at its ClientHello (144 bytes)"""
+    _fields_ = [("psk", ctypes.c_ubyte * 48), ("binder_transcript", ctypes.c_ubyte * 48),
+                ("hello_transcript", ctypes.c_ubyte * 48)]
+
+
 _MD_MAX = ctypes.c_ubyte * 64      # MBEDTLS_TLS1_3_MD_MAX_SIZE
 
 
@@ -295,6 +301,9 @@ SIGNATURES = {
     "tlsrec_tls13_keytab_derive_application": (_INT, [_VP, _U32, _U32, _INT, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_tls13_batch_verify_data": (_INT, [_INT, _VP, _VP, _VP, _U32, _VP]),
     "tlsrec_tls13_batch_derive_secret": (_INT, [_INT, _VP, _SZ, _VP, _VP, _VP, _U32, _VP]),
+    "tlsrec_tls13_batch_psk_binder": (_INT, [_INT, _U32, _INT, _VP, _VP, _VP, _VP, _U32, _VP]),
+    "tlsrec_tls13_keytab_derive_early": (_INT, [_VP, _U32, _U32, _INT, _U32, _INT, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tlsrec_tls13_batch_ticket_psk": (_INT, [_INT, _U32, _VP, _VP, _VP, _U32, _VP]),
     "tlsrec_tls_prf": (_INT, [_INT, _VP, _SZ, ctypes.c_char_p, _VP, _SZ, _VP, _SZ]),
     "tlsrec_tls12_compute_master": (_INT, [_INT, _VP, _SZ, _VP, _SZ, _INT, _VP]),
     "tlsrec_tls12_split_key_block": (_INT, [_INT, _VP, _SZ, _VP]),

@@ -22,6 +22,12 @@
  *                                               tlsrec_tls13_batch_verify_data, _batch_derive_secret:
  *                                               the ladder from PSK / (EC)DHE secret to the application
  *                                               keys, written for its fixed shapes like the TLS 1.2 batch
+ *   ssl_tls13_offered_psks_check_binder_match
+ *                  (ssl_tls13_server.c:404-457)  tlsrec_tls13_batch_psk_binder
+ *   ssl_tls13_generate_early_key :1086-1182,
+ *   ..._compute_early_transform  :1184-1225     tlsrec_tls13_keytab_derive_early
+ *   the "resumption" Expand-Label
+ *                (ssl_tls13_server.c:3219-3230)  tlsrec_tls13_batch_ticket_psk
  *
  * Every hash, HMAC and HKDF step runs in a kernel; the host only encodes the
  * HkdfLabel byte string (length, "tls13 " + label, context length), moves
@@ -1263,6 +1269,145 @@ template <class T> __global__ void __launch_bounds__(64) tls13_mac_kernel(Tls13M
     for (int j = 0; j < 16; j++) w[j] = 0;
 }
 
+/* ---- a resumed handshake: PSK binder, 0-RTT keys, ticket PSK ---------------
+ * An HkdfLabel up to and including its context-length byte is 2 (length) + 1
+ * (label length) + 6 ("tls13 ") + the label + 1 bytes, so the context starts
+ * at 10 + strlen(label): "res binder" / "ext binder" (10 characters) 20,
+ * "c e traffic" (11) 21, "e exp master" (12) 22, "resumption" (10) 20. */
+enum { OFF_BINDER = 20, OFF_E_TRAFFIC = 21, OFF_E_EXP_MASTER = 22, OFF_RESUMPTION = 20 };
+enum { AL_BINDERS = AL_MASTER, AL_OFFERED = AL_TRANSCRIPT };
+
+template <class T> struct Tls13EarlyArgs {
+    const tlsrec_tls13_psk_conn *conns;
+    const tlsrec_tls13_secret *offered;   /* with match, or both NULL */
+    tlsrec_tls13_secret *binders;         /* may be NULL */
+    uint32_t *match;
+    tlsrec_key_material *out;             /* staging area of slot `first`, one record per connection; NULL: binder only */
+    tlsrec_tls13_secret *early_traffic, *early_exporter;    /* read only with out; early_exporter may be NULL */
+    uint32_t count, head, key_cells, psk_len, aligned;
+    LadderConsts<T> k;
+    LabelW binder, c_e, e_exp;            /* "res binder" or "ext binder", "c e traffic", "e exp master" */
+    LadderLabels lb;                      /* key, iv, fin */
+};
+
+/* ssl_tls13_offered_psks_check_binder_match (ssl_tls13_server.c:404-457) and,
+ * with a.out, ssl_tls13_generate_early_key (ssl_tls13_keys.c:1086-1182), one
+ * connection per lane.  Compressions per connection: the binder
+ * 14 (Extract 2, midstates 2, binder key 2, midstates 2, finished key 2,
+ * midstates 2, MAC 2; the Early Secret's midstates also serve the early
+ * secrets); the early keys 10 more (two secrets 4, midstates 2, key 2, iv 2),
+ * 8 without the exporter: 14 / 22 / 24.  The two early secrets come before the
+ * binder key's midstates so that one pair of midstates is live at a time. */
+template <class T> __global__ void __launch_bounds__(64) tls13_early_kernel(Tls13EarlyArgs<T> a)
+{
+    typedef typename T::W W;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    const uint8_t *conn = reinterpret_cast<const uint8_t *>(a.conns + i);
+    const bool cal = (a.aligned & AL_CONNS) != 0;
+    W ip[8], op[8], w[16], x[T::HW], tr[T::HW], cs[T::HW];
+    {
+        /* Early Secret = Extract(0, PSK) */
+        uint32_t P[12];
+        load_cells<12>(conn, cal, P);
+        msg_block<T, 12>(w, P, a.psk_len, 0);
+        hmac_block<T>(a.k.zero_ip, a.k.zero_op, w, x);
+#pragma unroll
+        for (int j = 0; j < 12; j++) P[j] = 0;
+    }
+    hmac_mid<T>(x, ip, op);
+    if (a.out) {
+        load_digest<T>(conn + 96, cal, tr);
+        label_block<T, OFF_E_TRAFFIC, true>(w, a.c_e, tr);
+        hmac_block<T>(ip, op, w, cs);
+        store_secret<T>(a.early_traffic + i, (a.aligned & AL_TRAFFIC) != 0, cs);
+        if (a.early_exporter) {
+            label_block<T, OFF_E_EXP_MASTER, true>(w, a.e_exp, tr);
+            hmac_block<T>(ip, op, w, x);
+            store_secret<T>(a.early_exporter + i, (a.aligned & AL_AUX) != 0, x);
+        }
+    }
+    /* binder_key = Derive-Secret(Early Secret, "res binder" | "ext binder", ""), then
+     * ssl_tls13_calc_finished_core over the truncated ClientHello's hash */
+    label_block<T, OFF_BINDER, true>(w, a.binder, a.k.empty);
+    hmac_block<T>(ip, op, w, x);
+    hmac_mid<T>(x, ip, op);
+    label_block<T, OFF_FINISHED, false>(w, a.lb.fin, x);
+    hmac_block<T>(ip, op, w, x);
+    hmac_mid<T>(x, ip, op);
+    load_digest<T>(conn + 48, cal, tr);
+    digest_block<T>(w, tr);
+    hmac_block<T>(ip, op, w, x);
+    if (a.binders) store_secret<T>(a.binders + i, (a.aligned & AL_BINDERS) != 0, x);
+    if (a.match) {
+        /* mbedtls_ct_memcmp: the OR of the XOR of every cell, no early exit, no branch on the data */
+        load_digest<T>(a.offered[i].secret, (a.aligned & AL_OFFERED) != 0, tr);
+        W d = 0;
+#pragma unroll
+        for (int j = 0; j < T::HW; j++) d |= x[j] ^ tr[j];
+        uint32_t d32 = (uint32_t) d;
+        if constexpr (sizeof(W) == 8) d32 |= (uint32_t) ((uint64_t) d >> 32);
+        a.match[i] = d32 == 0 ? 1u : 0u;
+    }
+    if (a.out) traffic_side<T>(cs, a.lb, a.head, a.key_cells, a.out + i, nullptr, false);
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) { x[j] = 0; tr[j] = 0; cs[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
+/* psk[i] = HKDF-Expand-Label(res_master[i], "resumption", nonce i, H)
+ * (ssl_tls13_server.c:3219-3230): 4 compressions.  The 20 bytes of the
+ * HkdfLabel up to its context-length byte fill cells 0..4, so the nonce starts
+ * on cell 5; its length is wave-uniform, and the 0x01 that closes the
+ * HkdfLabel, the 0x80 and the length word (msg_block) move with it. */
+struct Tls13TicketArgs {
+    const tlsrec_tls13_secret *res_master;
+    const uint8_t *nonces;                /* 32 bytes per ticket, nonce_len used */
+    tlsrec_tls13_secret *psk;
+    uint32_t count, aligned, nonce_len;   /* AL_MASTER res_master, AL_TRANSCRIPT nonces, AL_AUX psk */
+    LabelW label;
+};
+
+template <class T> __global__ void __launch_bounds__(64) tls13_ticket_kernel(Tls13TicketArgs a)
+{
+    typedef typename T::W W;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    W ip[8], op[8], w[16], x[T::HW];
+    load_digest<T>(a.res_master[i].secret, (a.aligned & AL_MASTER) != 0, x);
+    hmac_mid<T>(x, ip, op);
+    uint32_t N[8], m[14];
+    load_cells<8>(a.nonces + 32 * (size_t) i, (a.aligned & AL_TRANSCRIPT) != 0, N);
+#pragma unroll
+    for (int c = 0; c < 5; c++) m[c] = a.label.c[c];
+#pragma unroll
+    for (int c = 0; c < 9; c++) {
+        const int rem = (int) a.nonce_len - 4 * c;          /* nonce bytes from this cell on */
+        const uint32_t v = c < 8 ? N[c] : 0u;
+        uint32_t y;
+        if (rem >= 4) y = v;
+        else if (rem >= 0) y = (rem ? v & ~(0xffffffffu >> (8 * rem)) : 0u) | (0x01u << (24 - 8 * rem));
+        else y = 0u;
+        m[5 + c] = y;
+    }
+    msg_block<T, 14>(w, m, OFF_RESUMPTION + a.nonce_len + 1, 0);
+    hmac_block<T>(ip, op, w, x);
+    store_secret<T>(a.psk + i, (a.aligned & AL_AUX) != 0, x);
+#pragma unroll
+    for (int j = 0; j < 8; j++) N[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 14; j++) m[j] = 0;
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) x[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+}
+
 } /* namespace tlsks */
 
 using namespace tlsks;
@@ -1977,6 +2122,125 @@ extern "C" int tlsrec_tls13_batch_derive_secret(int hash_alg, const unsigned cha
 {
     if (label_len > 12 || (!label && label_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
     return mac_launch(hash_alg, (uint32_t) label_len, label, secrets, transcripts, out, count, stream);
+}
+
+/* ---- a resumed handshake in batches (tls13_early_kernel, tls13_ticket_kernel) ---- */
+/* the BAD_INPUT_DATA checks the binder and the early-key calls share, in the header's order */
+static bool early_args_bad(bool null_array, uint32_t count, const void *offered, const void *binders, const void *match,
+                           uint32_t psk_len)
+{
+    if (null_array && count) return true;
+    if ((offered == nullptr) != (match == nullptr)) return true;
+    if (!binders && !match && count) return true;
+    return psk_len == 0 || psk_len > 48;
+}
+
+/* kt NULL: the binder alone, nothing staged */
+template <class T>
+static hipError_t early_launch(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, uint32_t psk_len,
+                               int psk_type, const tlsrec_tls13_psk_conn *conns, const tlsrec_tls13_secret *offered,
+                               tlsrec_tls13_secret *binders, uint32_t *match, tlsrec_tls13_secret *early_traffic,
+                               tlsrec_tls13_secret *early_exporter, hipStream_t st)
+{
+    Tls13EarlyArgs<T> a;
+    a.conns = conns;
+    a.offered = offered;
+    a.binders = binders;
+    a.match = match;
+    a.out = kt ? tlsrec__keytab_stage(kt) + first : nullptr;
+    a.early_traffic = early_traffic;
+    a.early_exporter = early_exporter;
+    a.count = count;
+    a.head = kt ? tls13_head(cipher) : 0u;
+    a.key_cells = kt ? tlsrec_cipher_keylen(cipher) / 4 : 0u;
+    a.psk_len = psk_len;
+    a.aligned = al(conns, AL_CONNS) | al(offered, AL_OFFERED) | al(binders, AL_BINDERS) | al(early_traffic, AL_TRAFFIC) |
+                al(early_exporter, AL_AUX);
+    a.k = ladder_consts<T>();
+    /* ssl_tls13_keys.c:879-895: "res binder" for a resumption PSK, "ext binder" for any other type */
+    a.binder = label_cells(T::HB, psk_type == TLSREC_TLS13_PSK_RESUMPTION ? "res binder" : "ext binder", 10, T::HB);
+    a.c_e = label_cells(T::HB, "c e traffic", 11, T::HB);
+    a.e_exp = label_cells(T::HB, "e exp master", 12, T::HB);
+    memset(&a.lb, 0, sizeof(a.lb));
+    a.lb.key = label_cells(kt ? tlsrec_cipher_keylen(cipher) : 0, "key", 3, 0);
+    a.lb.iv = label_cells(12, "iv", 2, 0);
+    a.lb.fin = label_cells(T::HB, "finished", 8, 0);
+    hipLaunchKernelGGL(tls13_early_kernel<T>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+extern "C" int tlsrec_tls13_batch_psk_binder(int hash_alg, uint32_t psk_len, int psk_type,
+                                             const tlsrec_tls13_psk_conn *conns, const tlsrec_tls13_secret *offered,
+                                             tlsrec_tls13_secret *binders, uint32_t *match, uint32_t count, void *stream)
+{
+    const int alg = alg_index(hash_alg);
+    if (alg < 0 || early_args_bad(!conns, count, offered, binders, match, psk_len)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (count == 0) return 0;
+    static const int device = tlsrec_device_check();     /* no key table vouches for a device here; asked once */
+    if (device != 0) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    hipStream_t st = (hipStream_t) stream;
+    const hipError_t e = alg == H_SHA384
+        ? early_launch<L384>(nullptr, 0, count, 0, psk_len, psk_type, conns, offered, binders, match, nullptr, nullptr, st)
+        : early_launch<L256>(nullptr, 0, count, 0, psk_len, psk_type, conns, offered, binders, match, nullptr, nullptr, st);
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+/* The derive kernel alone (see tlsrec__tls13_stage_keys). */
+extern "C" int tlsrec__tls13_stage_early_keys(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                              uint32_t psk_len, int psk_type, const tlsrec_tls13_psk_conn *conns,
+                                              const tlsrec_tls13_secret *offered, tlsrec_tls13_secret *binders,
+                                              uint32_t *match, tlsrec_tls13_secret *early_traffic,
+                                              tlsrec_tls13_secret *early_exporter, void *stream)
+{
+    if (!kt || early_args_bad(!conns || !early_traffic, count, offered, binders, match, psk_len))
+        return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const uint32_t cap = tlsrec_keytab_capacity(kt);
+    if (first > cap || count > cap - first) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (tlsrec_cipher_keylen(cipher) == 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (count == 0) return 0;
+    hipStream_t st = (hipStream_t) stream;
+    const hipError_t e = cipher == TLSREC_CIPHER_AES_256_GCM
+        ? early_launch<L384>(kt, first, count, cipher, psk_len, psk_type, conns, offered, binders, match, early_traffic,
+                             early_exporter, st)
+        : early_launch<L256>(kt, first, count, cipher, psk_len, psk_type, conns, offered, binders, match, early_traffic,
+                             early_exporter, st);
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls13_keytab_derive_early(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
+                                                uint32_t psk_len, int psk_type, const tlsrec_tls13_psk_conn *conns,
+                                                const tlsrec_tls13_secret *offered, tlsrec_tls13_secret *binders,
+                                                uint32_t *match, tlsrec_tls13_secret *early_traffic,
+                                                tlsrec_tls13_secret *early_exporter, void *stream)
+{
+    int r = tlsrec__tls13_stage_early_keys(kt, first, count, cipher, psk_len, psk_type, conns, offered, binders, match,
+                                           early_traffic, early_exporter, stream);
+    if (r == 0 && count) r = tlsrec__keytab_commit_staged(kt, first, count, cipher, (hipStream_t) stream);
+    return r;
+}
+
+extern "C" int tlsrec_tls13_batch_ticket_psk(int hash_alg, uint32_t nonce_len, const tlsrec_tls13_secret *res_master,
+                                             const uint8_t *nonces, tlsrec_tls13_secret *psk, uint32_t count,
+                                             void *stream)
+{
+    const int alg = alg_index(hash_alg);
+    if (alg < 0 || ((!res_master || !nonces || !psk) && count)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (nonce_len > 32) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (count == 0) return 0;
+    static const int device = tlsrec_device_check();
+    if (device != 0) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    Tls13TicketArgs a;
+    a.res_master = res_master;
+    a.nonces = nonces;
+    a.psk = psk;
+    a.count = count;
+    a.aligned = al(res_master, AL_MASTER) | al(nonces, AL_TRANSCRIPT) | al(psk, AL_AUX);
+    a.nonce_len = nonce_len;
+    a.label = label_cells(alg_len(alg), "resumption", 10, nonce_len);
+    hipStream_t st = (hipStream_t) stream;
+    if (alg == H_SHA384) hipLaunchKernelGGL(tls13_ticket_kernel<L384>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(tls13_ticket_kernel<L256>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
 }
 
 /* ======================================================================

@@ -187,3 +187,40 @@ def batch_derive_secret(hash_alg: int, label: bytes, secrets, transcripts, out, 
     """out[i] = Derive-Secret(secrets[i], label, hashed context transcripts[i]); label of at most 12 bytes"""
     _chk("tlsrec_tls13_batch_derive_secret", _abi.load().tlsrec_tls13_batch_derive_secret(
         hash_alg, _b(label), len(label), _ptr(secrets), _ptr(transcripts), _ptr(out), count, _stream(stream)))
+
+
+# ---- a resumed handshake in batches ------------------------------------------------
+#    ssl_tls13_offered_psks_check_binder_match (ssl_tls13_server.c:404)  -> batch_psk_binder
+#    ssl_tls13_generate_early_key (:1086) + compute_early_transform (:1184) -> keytab_derive_early
+#    the "resumption" Expand-Label (ssl_tls13_server.c:3219)             -> batch_ticket_psk
+PSK_CONN_BYTES = ctypes.sizeof(_abi.CTls13PskConn)   # 144: psk[48] || binder_transcript[48] || hello_transcript[48]
+TICKET_NONCE_BYTES = 32                              # MBEDTLS_SSL_TLS1_3_TICKET_NONCE_LENGTH
+
+
+def batch_psk_binder(hash_alg: int, psk_len: int, psk_type: int, conns, offered, binders, match, count: int,
+                     stream=None) -> None:
+    """`conns`: device buffer of count x 144 bytes (tlsrec_tls13_psk_conn), only
+    read.  binders (or None): count x 48 bytes.  offered (count x 48 bytes) and
+    match (count x uint32: 1 where the first Hash.length bytes of offered[i] are
+    the binder) go together; a client computing its own binders passes None, None."""
+    _chk("tlsrec_tls13_batch_psk_binder", _abi.load().tlsrec_tls13_batch_psk_binder(
+        hash_alg, psk_len, psk_type, _ptr(conns), _ptr(offered), _ptr(binders), _ptr(match), count, _stream(stream)))
+
+
+def keytab_derive_early(kt: KeyTable, first: int, count: int, cipher: int, psk_len: int, psk_type: int, conns, offered,
+                        binders, match, early_traffic, early_exporter, stream=None) -> None:
+    """batch_psk_binder and, in the same pass, c e traffic -> early_traffic, e exp
+    master -> early_exporter (or None), both count x 48 bytes, and the key / iv of
+    c e traffic into slot first + i (client_write).  The slot is loaded whether
+    or not the binder matched: where match[i] == 0 the connection is dropped and
+    slot first + i must not be used."""
+    _chk("tlsrec_tls13_keytab_derive_early", _abi.load().tlsrec_tls13_keytab_derive_early(
+        _h(kt), first, count, cipher, psk_len, psk_type, _ptr(conns), _ptr(offered), _ptr(binders), _ptr(match),
+        _ptr(early_traffic), _ptr(early_exporter), _stream(stream)))
+
+
+def batch_ticket_psk(hash_alg: int, nonce_len: int, res_master, nonces, psk, count: int, stream=None) -> None:
+    """psk[i] = HKDF-Expand-Label(res_master[i], "resumption", nonce i, Hash.length);
+    `nonces`: count x 32 bytes on the device, the first nonce_len (0..32) of each used"""
+    _chk("tlsrec_tls13_batch_ticket_psk", _abi.load().tlsrec_tls13_batch_ticket_psk(
+        hash_alg, nonce_len, _ptr(res_master), _ptr(nonces), _ptr(psk), count, _stream(stream)))

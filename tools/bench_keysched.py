@@ -29,6 +29,14 @@ derive kernel alone, the single-shot ladder + tlsrec_keytab_load it replaces
 on at most 2 048 connections, and the tlsrec_tls12_keytab_derive AES-128-GCM
 kernel under the same hash for a ns-per-compression yardstick.
 
+--tls13-early: a resumed handshake's batches over 64 K connections of one
+(cipher, psk_len): tlsrec_tls13_keytab_derive_early (--no-keys:
+tlsrec_tls13_batch_psk_binder), its derive kernel alone, the binder-only kernel,
+tlsrec_tls13_batch_ticket_psk, the host path it replaces on at most 2 048
+connections (create_psk_binder + derive_early_secrets + make_traffic_keys per
+connection, then one tlsrec_keytab_load), and the handshake-stage derive kernel
+under the same hash for the ns-per-compression yardstick.
+
 Prints one JSON line; the whole call and the derive kernel alone are timed
 with HIP events on the call's stream, the key-setup kernel is the difference.
 
@@ -36,6 +44,7 @@ with HIP events on the call's stream, the key-setup kernel is the difference.
     python tools/bench_keysched.py --tls12 [--prf sha256|sha384] [--count 65536] [--cipher 1]
     python tools/bench_keysched.py --tls12 --cbc-mac 2 [--etm] [--count 65536]
     python tools/bench_keysched.py --tls13-handshake [--cipher 1|2] [--psk-len 32] [--shared-len 32]
+    python tools/bench_keysched.py --tls13-early [--cipher 1|2|3] [--psk-len 32] [--no-keys]
 """
 import argparse
 import ctypes
@@ -432,11 +441,142 @@ def main_tls13_handshake(a):
                                     "tls13 handshake stage + key setup")}))
 
 
+def host_tls13_early_leg(hash_alg, cipher, psk_len, raw, sample, keys):
+    """The path without the batch, for `sample` connections: the single-shot
+    binder per connection and, with `keys`, the Early Secret, its two secrets
+    and the key / iv (a synchronised job chain per step, every secret back on
+    the host), then one tlsrec_keytab_load."""
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import keysched as K
+    H, kl = K.HASH_LEN[hash_alg], M.KEYLEN[cipher]
+    kt = M.KeyTable(sample)
+    K.evolve_secret(hash_alg, None, None)                        # the control-path stream and arena exist
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pairs = []
+    for i in range(sample):
+        c = raw[144 * i:144 * i + 144]
+        K.create_psk_binder(hash_alg, c[:psk_len], K.PSK_RESUMPTION, c[48:48 + H])
+        if keys:
+            early = K.evolve_secret(hash_alg, None, c[:psk_len])
+            ce, _ = K.derive_early_secrets(hash_alg, early, c[96:96 + H])
+            ck, civ, _, _ = K.make_traffic_keys(hash_alg, ce, ce, kl, 12)
+            pairs.append((ck, civ))
+    ladder = time.perf_counter() - t0
+    load = 0.0
+    if keys:
+        km = np.concatenate([M.key_material(cipher, M.VERSION_TLS1_3, k, iv) for k, iv in pairs])
+        t0 = time.perf_counter()
+        kt.load(km)
+        torch.cuda.synchronize()
+        load = time.perf_counter() - t0
+    kt.close()
+    return {"value": round(sample / (ladder + load)), "unit": "connections/s", "sample_connections": sample,
+            "us_per_connection": round((ladder + load) / sample * 1e6, 2), "ladder_seconds": round(ladder, 4),
+            "keytab_load_seconds": round(load, 4),
+            "what": "per connection create_psk_binder" + (", evolve_secret (the Early Secret derive_early_secrets takes), "
+                    "derive_early_secrets, make_traffic_keys, then one tlsrec_keytab_load of the records" if keys else "")
+                    + "; wall time"}
+
+
+def main_tls13_early(a):
+    """tlsrec_tls13_keytab_derive_early (--no-keys: tlsrec_tls13_batch_psk_binder),
+    its derive kernel alone, the binder-only kernel, tlsrec_tls13_batch_ticket_psk,
+    the host path they replace, and the handshake-stage derive kernel of the same
+    run under the same hash as the ns-per-compression yardstick."""
+    from tools import rowlib
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import keysched as K
+    from mbedtls_amd.batch import _ptr, _stream
+    from tests.prng import prng_array
+    dev = torch.device("cuda")
+    L = M.load()
+    vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+    L.tlsrec__tls13_stage_hs_keys.restype = ci
+    L.tlsrec__tls13_stage_hs_keys.argtypes = [vp, u32, u32, ci, u32, u32, vp, vp, vp, vp, vp]
+    L.tlsrec__tls13_stage_early_keys.restype = ci
+    L.tlsrec__tls13_stage_early_keys.argtypes = [vp, u32, u32, ci, u32, ci, vp, vp, vp, vp, vp, vp, vp]
+    cipher, pl, n, keys = a.cipher, a.psk_len, a.count, not a.no_keys
+    sha384 = cipher == M.CIPHER_AES_256_GCM
+    hname, alg = ("sha384", K.ALG_SHA_384) if sha384 else ("sha256", K.ALG_SHA_256)
+    raw = prng_array(0x7155, n * 144)
+    conns = torch.from_numpy(raw).to(dev)
+    hconns = torch.from_numpy(prng_array(0x7153, n * 176)).to(dev)
+    nonces = torch.from_numpy(prng_array(0x7156, n * 32)).to(dev)
+
+    def buf(k):
+        return torch.zeros(k * 48, dtype=torch.uint8, device=dev)
+
+    off, bd, ce, ex, rm, psk, hs, fin, ms = buf(n), buf(n), buf(n), buf(n), buf(n), buf(n), buf(2 * n), buf(2 * n), buf(n)
+    rm.copy_(torch.from_numpy(prng_array(0x7157, n * 48)).to(dev))
+    mt = torch.zeros(n, dtype=torch.int32, device=dev)
+    kt, kths = M.KeyTable(n), M.KeyTable(2 * n)
+    res = K.PSK_RESUMPTION
+    sl = 48 if sha384 else 32
+
+    def ok(r):
+        assert r == 0, r
+
+    s = _stream(None)
+    K.batch_psk_binder(alg, pl, res, conns, None, off, None, n)      # the offered binders are the right ones
+    legs = {
+        "binder": lambda: K.batch_psk_binder(alg, pl, res, conns, off, bd, mt, n),
+        "ticket_psk": lambda: K.batch_ticket_psk(alg, 32, rm, nonces, psk, n),
+        "hs_derive_kernel": lambda: ok(L.tlsrec__tls13_stage_hs_keys(kths.handle, 0, n, cipher, pl, sl, _ptr(hconns),
+                                                                      _ptr(hs), _ptr(fin), _ptr(ms), s)),
+    }
+    if keys:
+        legs["early_derive_kernel"] = lambda: ok(L.tlsrec__tls13_stage_early_keys(
+            kt.handle, 0, n, cipher, pl, res, _ptr(conns), _ptr(off), _ptr(bd), _ptr(mt), _ptr(ce), _ptr(ex), s))
+        legs["early_call"] = lambda: K.keytab_derive_early(kt, 0, n, cipher, pl, res, conns, off, bd, mt, ce, ex)
+    ms_, wall = {}, {}
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()
+        ms_[name], wall[name] = rowlib.event_timed(fn, a.steps)
+    assert int(mt.sum().item()) == n
+    comp = {"binder": 14, "ticket_psk": 4, "hs_derive_kernel": 8 + 2 + 2 + 4 + 6 + 16, "early_derive_kernel": 24}
+    ns = {k: ms_[k] * 1e6 / n / comp[k] for k in comp if k in ms_}
+    host = None if a.no_cpu else host_tls13_early_leg(alg, cipher, pl, raw.tobytes(), min(2048, n), keys)
+    call = "early_call" if keys else "binder"
+    kern = "early_derive_kernel" if keys else "binder"
+    cps = n / (ms_[call] / 1e3)
+    print(json.dumps({
+        "metric": "TLS 1.3 PSK binder checks" + (" and 0-RTT key derivations into the key table" if keys else "") +
+                  " per second", "value": round(cps), "unit": "connections/s", "count": n, "slots": n if keys else 0,
+        "cipher": cipher, "hash": hname, "psk_len": pl, "keys": int(keys),
+        "call": "tlsrec_tls13_keytab_derive_early" if keys else "tlsrec_tls13_batch_psk_binder",
+        "ms_per_batch_events": round(ms_[call], 4), "ms_per_batch_wall": round(wall[call] * 1e3, 4),
+        "derive_kernel_ms": round(ms_[kern], 4), "key_setup_ms": round(ms_[call] - ms_[kern], 4),
+        "compressions_per_connection": comp[kern], "derive_kernel_ns_per_compression": round(ns[kern], 4),
+        "per_compression_vs_hs_kernel_same_run": round(ns[kern] / ns["hs_derive_kernel"], 3),
+        "binder_only": {"ms": round(ms_["binder"], 4), "compressions_per_connection": 14,
+                        "ns_per_compression": round(ns["binder"], 4),
+                        "per_compression_vs_hs_kernel_same_run": round(ns["binder"] / ns["hs_derive_kernel"], 3)},
+        "batch_ticket_psk": {"count": n, "nonce_len": 32, "ms": round(ms_["ticket_psk"], 4),
+                             "ns_per_compression": round(ns["ticket_psk"], 4)},
+        "hs_kernel_same_run": {"psk_len": pl, "shared_len": sl, "derive_kernel_ms": round(ms_["hs_derive_kernel"], 4),
+                               "compressions_per_connection": comp["hs_derive_kernel"],
+                               "derive_kernel_ns_per_compression": round(ns["hs_derive_kernel"], 4)},
+        "host_path": host, "speedup_vs_host_path": round(cps / host["value"], 1) if host else None,
+        "roofline": rowlib.roofline((144 + 48 + 4 + (3 * 48 + 64 if keys else 48)) * n, ms_[call], "per connection: the "
+                                    "144-byte tlsrec_tls13_psk_conn and the 48-byte offered binder read, the match "
+                                    "word, the binder" + (", two 48-byte secrets and one 64-byte key record" if keys
+                                                          else "") + " written; the key-table slots the key setup "
+                                    "builds are not counted", "tls13 early stage" + (" + key setup" if keys else ""))}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tls13-early", action="store_true",
+                    help="the resumed-handshake batches (tlsrec_tls13_keytab_derive_early, _batch_psk_binder, "
+                         "_batch_ticket_psk)")
+    ap.add_argument("--no-keys", action="store_true", help="--tls13-early: the binder alone, no table")
     ap.add_argument("--tls13-handshake", action="store_true",
                     help="the TLS 1.3 ladder batches (tlsrec_tls13_keytab_derive_handshake / _application)")
-    ap.add_argument("--psk-len", type=int, default=32, help="--tls13-handshake: 0..48")
+    ap.add_argument("--psk-len", type=int, default=32, help="--tls13-handshake: 0..48; --tls13-early: 1..48")
     ap.add_argument("--shared-len", type=int, default=32, help="--tls13-handshake: 0, 32, 48, 56 or 66")
     ap.add_argument("--count", type=int, default=65536)
     ap.add_argument("--cipher", type=int, default=None, help="default 2 (with --cbc-mac: the suite's, 23 or 24)")
@@ -451,6 +591,9 @@ def main():
                     help="--tls12: an AES-CBC + HMAC suite (1 SHA-1, 2 SHA-256, 3 SHA-384), tlsrec_tls12_keytab_derive_cbc")
     ap.add_argument("--etm", action="store_true", help="--cbc-mac: encrypt-then-MAC slots")
     a = ap.parse_args()
+    if a.tls13_early:
+        a.cipher = 1 if a.cipher is None else a.cipher
+        return main_tls13_early(a)
     if a.tls13_handshake:
         a.cipher = 1 if a.cipher is None else a.cipher
         return main_tls13_handshake(a)

@@ -685,6 +685,85 @@ typedef struct tlsrec_tls12_conn {
 int tlsrec_tls12_keytab_derive(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher,
                                int prf, const tlsrec_tls12_conn *conns, void *stream);
 
+/* One TLS 1.2 / DTLS 1.2 connection at its key exchange: 240 bytes, device-resident, only read */
+typedef struct tlsrec_tls12_pms_conn {
+    uint8_t premaster[128];    /* pms_len bytes used */
+    uint8_t randbytes[64];     /* client_random || server_random (handshake->randbytes before the swap) */
+    uint8_t session_hash[48];  /* extended_ms only: Hash(handshake messages), Hash.length bytes used */
+} tlsrec_tls12_pms_conn;
+
+/* Batch, master secret: ssl_compute_master (ssl_tls.c:6251-6452) for each of `count`
+ * connections, in one kernel:
+ *   master = PRF(premaster[0..pms_len), "master secret", randbytes)[0..48]
+ * or with extended_ms != 0 (RFC 7627 section 4, ssl_tls.c:6284-6305)
+ *   master = PRF(premaster[0..pms_len), "extended master secret", session_hash)[0..48]
+ * where the session hash is Hash.length bytes, 32 under TLSREC_TLS_PRF_SHA256 and 48
+ * under _SHA384.  out[i] is master || server_random || client_random: the swap of
+ * ssl_tls.c:6479-6488 is done here, so `out` is the `conns` argument of
+ * tlsrec_tls12_keytab_derive / _derive_cbc and of tlsrec_tls12_batch_verify_data on the
+ * same stream, with nothing in between.  pms_len (1..128) and extended_ms hold for the
+ * whole call; bytes of premaster past pms_len and of session_hash past Hash.length are
+ * not looked at.  This covers the (EC)DHE and RSA premasters and the RFC 4279 forms
+ * tlsrec_tls12_psk_premaster builds.
+ * The one divergence: a premaster longer than 128 bytes (FFDH: the size of the group's
+ * prime) is TLSREC_ERR_SSL_FEATURE_UNAVAILABLE here and stays with
+ * tlsrec_tls12_compute_master.
+ * The reference zeroizes handshake->premaster (:6447); conns is only read here, so the
+ * caller wipes it once the stream has passed the call (a hipMemsetAsync on the same
+ * stream does).  Both arrays are device arrays.  Asynchronous on `stream`, no host round
+ * trip; conns must stay valid until the stream reaches the call.
+ * Errors, in this order: TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for TLSREC_TLS_PRF_NONE or
+ * an unknown prf (decided before the GPU is touched); TLSREC_ERR_SSL_BAD_INPUT_DATA for
+ * conns or out NULL with count != 0, then for pms_len == 0;
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for pms_len > 128.  count == 0 then returns 0 and
+ * launches nothing. */
+int tlsrec_tls12_batch_compute_master(int prf, uint32_t pms_len, int extended_ms,
+                                      const tlsrec_tls12_pms_conn *conns,
+                                      tlsrec_tls12_conn *out, uint32_t count, void *stream);
+
+/* ssl_calc_finished_tls_generic, ssl_tls.c:7209-7261:
+ *   out = PRF(master, "client finished" | "server finished", transcript_hash)[0..12]
+ * `from` (TLSREC_IS_CLIENT / TLSREC_IS_SERVER) names the sender of the Finished message;
+ * transcript_hash is Hash.length bytes.  Single-shot, like tlsrec_tls12_compute_master.
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for the prf, then TLSREC_ERR_SSL_BAD_INPUT_DATA for
+ * another `from` or a NULL pointer. */
+int tlsrec_tls12_calc_finished(int prf, const unsigned char master[48], const unsigned char *transcript_hash,
+                               int from, unsigned char out[12]);
+
+/* Batch, Finished: tlsrec_tls12_calc_finished for each of `count` connections in one
+ * kernel, and the check of mbedtls_ssl_parse_finished (ssl_tls.c:7488, mbedtls_ct_memcmp
+ * at :7530):
+ *   verify_data = PRF(conns[i].master, label of `from`, transcripts[i])[0..12]
+ *                                                  -> verify[16 i .. 16 i + 12), then 4 zero bytes
+ *   match[i] = 1 if offered[16 i .. 16 i + 12) equals it, else 0
+ * Only `master` is read from a tlsrec_tls12_conn; a transcripts element holds Hash.length
+ * bytes.  The compare ORs the XOR of the three words, with no early exit and no branch on
+ * the data; bytes 12..15 of an offered element are not looked at.  offered and match are
+ * both given or both NULL (an endpoint computing its own Finished passes NULL, NULL);
+ * verify may be NULL only when match is given.  Every array is a device array; match is
+ * one uint32_t per connection.  Asynchronous on `stream`, no host round trip.
+ * Errors, in this order: TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for the prf;
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA for a `from` other than the two constants, for conns or
+ * transcripts NULL with count != 0, for only one of offered and match given, for verify
+ * and match both NULL with count != 0.  count == 0 then returns 0. */
+int tlsrec_tls12_batch_verify_data(int prf, int from, const tlsrec_tls12_conn *conns,
+                                   const tlsrec_tls13_secret *transcripts,
+                                   const uint8_t *offered /* count x 16 bytes, 12 used */,
+                                   uint8_t *verify /* count x 16 bytes */,
+                                   uint32_t *match, uint32_t count, void *stream);
+
+/* Host-only, no GPU: the premaster of the PSK key exchanges (RFC 4279 section 2, what
+ * PSA's PSK_TO_MS builds at ssl_tls.c:6307-6366),
+ *   uint16(other_len) || other || uint16(psk_len) || psk
+ * where `other` is the (EC)DHE shared secret, or for plain PSK (other NULL, other_len 0)
+ * psk_len zero bytes.  *olen receives the length, the pms_len of
+ * tlsrec_tls12_batch_compute_master.  TLSREC_ERR_SSL_BAD_INPUT_DATA for psk, out or olen
+ * NULL, for psk_len == 0, for other NULL with other_len != 0 or a length past 65535;
+ * TLSREC_ERR_SSL_BUFFER_TOO_SMALL when out_size is short (nothing written). */
+int tlsrec_tls12_psk_premaster(const unsigned char *other, size_t other_len,
+                               const unsigned char *psk, size_t psk_len,
+                               unsigned char *out, size_t out_size, size_t *olen);
+
 /* ---- CBC + HMAC slots: AES, ARIA, Camellia (TLS 1.2 / DTLS 1.2) ----------
  * (ARIA and Camellia: the ids 26..29 above, each with its one MAC; whatever
  * this section says of a CBC slot holds for them.  Sizes depend on the MAC and

@@ -141,6 +141,12 @@ class CTls12Conn(ctypes.Structure):
     _fields_ = [("master", ctypes.c_ubyte * 48), ("randbytes", ctypes.c_ubyte * 64)]
 
 
+class CTls12PmsConn(ctypes.Structure):
+    """tlsrec_tls12_pms_conn: one TLS 1.2 / DTLS 1.2 connection at its key exchange (240 bytes)"""
+    _fields_ = [("premaster", ctypes.c_ubyte * 128), ("randbytes", ctypes.c_ubyte * 64),
+                ("session_hash", ctypes.c_ubyte * 48)]
+
+
 class CTls13Secret(ctypes.Structure):
     """tlsrec_tls13_secret: one secret of the TLS 1.3 ladder (48 bytes, Hash.length used)"""
     _fields_ = [("secret", ctypes.c_ubyte * 48)]
@@ -310,6 +316,10 @@ SIGNATURES = {
     "tlsrec_tls12_make_keys": (_INT, [_INT, _INT, _VP, _VP, _VP]),
     "tlsrec_tls12_export_keying_material": (_INT, [_INT, _VP, _VP, _VP, _SZ, _VP, _SZ, _INT, _VP, _SZ]),
     "tlsrec_tls12_keytab_derive": (_INT, [_VP, _U32, _U32, _INT, _INT, _VP, _VP]),
+    "tlsrec_tls12_batch_compute_master": (_INT, [_INT, _U32, _INT, _VP, _VP, _U32, _VP]),
+    "tlsrec_tls12_calc_finished": (_INT, [_INT, _VP, _VP, _INT, _VP]),
+    "tlsrec_tls12_batch_verify_data": (_INT, [_INT, _INT, _VP, _VP, _VP, _VP, _VP, _U32, _VP]),
+    "tlsrec_tls12_psk_premaster": (_INT, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _VP]),
     "tlsrec_ticket_write": (_INT, [_VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_ticket_parse": (_INT, [_VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_stream_decrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),

@@ -1408,6 +1408,321 @@ template <class T> __global__ void __launch_bounds__(64) tls13_ticket_kernel(Tls
     for (int j = 0; j < 16; j++) w[j] = 0;
 }
 
+/* ---- TLS 1.2 / DTLS 1.2 handshake: master secret, Finished verify_data -----
+ * ssl_compute_master (ssl_tls.c:6251-6452) and ssl_calc_finished_tls_generic
+ * (:7209-7261) with the constant-time check of mbedtls_ssl_parse_finished
+ * (:7530), one connection per lane, on the blocks of the ladder above.  Both
+ * are PRF(secret, label, seed) = P_hash(secret, label || seed) (RFC 5246
+ * section 5) cut to 48 or 12 bytes: two midstates of the secret, then per
+ * iteration A(i) = HMAC(A(i-1)) and HMAC(A(i) || label || seed).
+ *
+ * label || seed, N bytes in the cells S[]:
+ *   "master secret" || randbytes              13 + 64 = 77
+ *   "extended master secret" || session_hash  22 + 32 = 54, 22 + 48 = 70
+ *   "client finished" | "server finished" || transcript hash  15 + 32 = 47, 15 + 48 = 63
+ * N is a constant of the instantiation, so the padding and the length word of
+ * every block are constants.  Compressions per connection:
+ *   A(1): 1, or 2 where N + 9 > 64 (SHA-256, 77);  A(i > 1): 1;  each outer hash: 1
+ *   HMAC(A || S): Hash.length + N bytes, 2 inner blocks, or 1 where it pads
+ *   into one (SHA-384, 48 + 63 + 17 = 128)
+ *   master, SHA-256: 2 + (3 | 2) + 3 + 2 + 3 = 13 | 12, and 2 | 3 more where the
+ *   premaster is longer than the block and is hashed first;  SHA-384: 2 + 2 + 3 = 7
+ *   verify_data: SHA-256 2 + 2 + 3 = 7;  SHA-384 2 + 2 + 2 = 6 */
+
+/* block `blk` of the n-byte message in m[] (n wave-uniform, blk a constant):
+ * bytes past n are masked off.  PAD: the blocks of a plain hash, with 0x80
+ * after the message and its length in bits closing the first block that has
+ * room for both.  Without PAD the zero-padded block of an HMAC key. */
+template <class T, int NC, bool PAD>
+__device__ __forceinline__ void key_block(typename T::W (&w)[16], const uint32_t (&m)[NC], uint32_t n, int blk)
+{
+    constexpr int CPB = T::BB / 4;
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int c = 0; c < CPB; c++) {
+        const int g = blk * CPB + c;
+        const int rem = (int) n - 4 * g;
+        const uint32_t v = g < NC ? m[g] : 0u;
+        uint32_t x;
+        if (rem >= 4) x = v;
+        else if (rem > 0) x = (v & ~(0xffffffffu >> (8 * rem))) | (PAD ? 0x80u << (24 - 8 * rem) : 0u);
+        else x = PAD && rem == 0 ? 0x80000000u : 0u;
+        or_cell<T>(w, c, x);
+    }
+    const int end = (int) n + 1 + (int) T::LENB;
+    if (PAD && end <= (blk + 1) * (int) T::BB && end > blk * (int) T::BB) w[15] = (typename T::W) (n * 8);
+}
+
+/* the two midstates of HMAC under the zero-padded key block kb (consumed): 2 compressions */
+template <class T>
+__device__ __forceinline__ void hmac_mid_block(typename T::W (&kb)[16], typename T::W (&ip)[8], typename T::W (&op)[8])
+{
+    typedef typename T::W W;
+    W w[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = kb[j] ^ (W) 0x3636363636363636ULL;
+#pragma unroll
+    for (int j = 0; j < 8; j++) ip[j] = T::iv(j);
+    sha_compress<typename T::S>(ip, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = kb[j] ^ (W) 0x5c5c5c5c5c5c5c5cULL;
+#pragma unroll
+    for (int j = 0; j < 8; j++) op[j] = T::iv(j);
+    sha_compress<typename T::S>(op, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++) { w[j] = 0; kb[j] = 0; }
+}
+
+/* The first OUTC cells of P_hash over the N bytes of S under the midstates ip / op. */
+template <class T, int N, int OUTC>
+__device__ __forceinline__ void tls12_p_hash(const typename T::W (&ip)[8], const typename T::W (&op)[8],
+                                             const uint32_t (&S)[20], uint32_t (&out)[OUTC])
+{
+    typedef typename T::W W;
+    constexpr int ITERS = (4 * OUTC + T::HB - 1) / T::HB;
+    constexpr int NC = T::HC + 20, L = T::HB + N;      /* A || S */
+    static_assert(N <= 80 && N + 1 + T::LENB <= 2 * T::BB && L + 1 + T::LENB <= 2 * T::BB, "one or two inner blocks");
+    W w[16], st[8], A[T::HW];
+    uint32_t C[NC];
+#pragma unroll
+    for (int j = 0; j < T::HC; j++) C[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 20; j++) C[T::HC + j] = S[j];
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) A[j] = 0;
+#pragma unroll 1
+    for (int it = 0; it < ITERS; it++) {
+        /* A(it + 1) = HMAC(A(it)); A(0) is S */
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        if (it == 0) {
+            msg_block<T, 20>(w, S, N, 0);
+            sha_compress<typename T::S>(st, w);
+            if constexpr (N + 1 + T::LENB > T::BB) {
+                msg_block<T, 20>(w, S, N, 1);
+                sha_compress<typename T::S>(st, w);
+            }
+        } else {
+            digest_block<T>(w, A);
+            sha_compress<typename T::S>(st, w);
+        }
+        hmac_outer<T>(op, st, A);
+        /* output block = HMAC(A || S) */
+#pragma unroll
+        for (int c = 0; c < T::HC; c++) C[c] = cell<T, T::HW>(A, c);
+#pragma unroll
+        for (int j = 0; j < 8; j++) st[j] = ip[j];
+        msg_block<T, NC>(w, C, L, 0);
+        sha_compress<typename T::S>(st, w);
+        if constexpr (L + 1 + T::LENB > T::BB) {
+            msg_block<T, NC>(w, C, L, 1);
+            sha_compress<typename T::S>(st, w);
+        }
+        W D[T::HW];
+        hmac_outer<T>(op, st, D);
+#pragma unroll
+        for (int q = 0; q < ITERS; q++) {
+            if (it == q) {
+#pragma unroll
+                for (int c = 0; c < T::HC; c++)
+                    if (q * T::HC + c < OUTC) out[q * T::HC + c] = cell<T, T::HW>(D, c);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < T::HW; j++) D[j] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) st[j] = 0;
+#pragma unroll
+    for (int j = 0; j < T::HW; j++) A[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int j = 0; j < NC; j++) C[j] = 0;
+}
+
+struct Tls12MasterArgs {
+    const tlsrec_tls12_pms_conn *conns;
+    tlsrec_tls12_conn *out;
+    uint32_t count, pms_len, aligned;     /* AL_CONNS conns, AL_AUX out */
+};
+
+/* EMS: "extended master secret" over the session hash (RFC 7627 section 4,
+ * ssl_tls.c:6284-6305), else "master secret" over randbytes (:6269).  The
+ * premaster is the HMAC key: zero-padded to the block, or under SHA-256 its
+ * digest where it is longer than 64 bytes (RFC 2104; two inner blocks up to
+ * 119 bytes, three from 120).  Only the 16-byte groups that hold premaster
+ * bytes are loaded. */
+template <class T, bool EMS> __global__ void __launch_bounds__(64) tls12_master_kernel(Tls12MasterArgs a)
+{
+    typedef typename T::W W;
+    static_assert(sizeof(tlsrec_tls12_pms_conn) == 240 && offsetof(tlsrec_tls12_pms_conn, randbytes) == 128 &&
+                  offsetof(tlsrec_tls12_pms_conn, session_hash) == 192 && sizeof(tlsrec_tls12_conn) == 112,
+                  "tlsrec_tls12_pms_conn / tlsrec_tls12_conn layout");
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    const uint8_t *conn = reinterpret_cast<const uint8_t *>(a.conns + i);
+    const bool cal = (a.aligned & AL_CONNS) != 0;
+    const uint32_t n = a.pms_len;
+    W ip[8], op[8], w[16];
+    /* every load of the connection is issued before the first compression: one wait on memory, not three */
+    uint32_t R[16], S[20], X[12], Hs[EMS ? (int) T::HC : 1];
+    load_cells<16>(conn + 128, cal, R);
+    if constexpr (EMS) load_cells<T::HC>(conn + 192, cal, Hs);
+    {
+        uint32_t P[32];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            uint32_t g[4] = { 0u, 0u, 0u, 0u };
+            if ((uint32_t) (16 * k) < n) load_cells<4>(conn + 16 * k, cal, g);
+#pragma unroll
+            for (int j = 0; j < 4; j++) { P[4 * k + j] = g[j]; g[j] = 0; }
+        }
+        W kb[16];
+        bool hashed = false;
+        if constexpr (sizeof(W) == 4) hashed = n > T::BB;
+        if (hashed) {
+            W st[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) st[j] = T::iv(j);
+            key_block<T, 32, true>(w, P, n, 0);
+            sha_compress<typename T::S>(st, w);
+            key_block<T, 32, true>(w, P, n, 1);
+            sha_compress<typename T::S>(st, w);
+            if (n + 1 + T::LENB > 2 * T::BB) {
+                key_block<T, 32, true>(w, P, n, 2);
+                sha_compress<typename T::S>(st, w);
+            }
+#pragma unroll
+            for (int j = 0; j < 16; j++) kb[j] = j < T::HW ? st[j] : (W) 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) st[j] = 0;
+        } else {
+            key_block<T, 32, false>(kb, P, n, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < 32; j++) P[j] = 0;
+        hmac_mid_block<T>(kb, ip, op);
+    }
+    constexpr int N = EMS ? 22 + (int) T::HB : 77;
+    if constexpr (EMS) {
+        S[0] = 0x65787465u;      /* "exte" */
+        S[1] = 0x6e646564u;      /* "nded" */
+        S[2] = 0x206d6173u;      /* " mas" */
+        S[3] = 0x74657220u;      /* "ter " */
+        S[4] = 0x73656372u;      /* "secr" */
+        S[5] = 0x65740000u | (Hs[0] >> 16);     /* "et" */
+#pragma unroll
+        for (int k = 1; k < T::HC; k++) S[5 + k] = (Hs[k - 1] << 16) | (Hs[k] >> 16);
+        S[5 + T::HC] = Hs[T::HC - 1] << 16;
+#pragma unroll
+        for (int k = 6 + T::HC; k < 20; k++) S[k] = 0;
+    } else {
+        S[0] = 0x6d617374u;      /* "mast" */
+        S[1] = 0x65722073u;      /* "er s" */
+        S[2] = 0x65637265u;      /* "ecre" */
+        S[3] = 0x74000000u | (R[0] >> 8);       /* "t" */
+#pragma unroll
+        for (int k = 1; k < 16; k++) S[3 + k] = (R[k - 1] << 24) | (R[k] >> 8);
+        S[19] = R[15] << 24;
+    }
+    tls12_p_hash<T, N, 12>(ip, op, S, X);
+    /* master || server_random || client_random: the swap of ssl_tls.c:6479-6488 */
+    uint32_t o[28];
+#pragma unroll
+    for (int c = 0; c < 12; c++) o[c] = __builtin_bswap32(X[c]);
+#pragma unroll
+    for (int c = 0; c < 8; c++) { o[12 + c] = __builtin_bswap32(R[8 + c]); o[20 + c] = __builtin_bswap32(R[c]); }
+    if (a.aligned & AL_AUX) {
+        uint4 *q = reinterpret_cast<uint4 *>(a.out + i);
+#pragma unroll
+        for (int k = 0; k < 7; k++) q[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    } else {
+        uint8_t *b = reinterpret_cast<uint8_t *>(a.out + i);
+#pragma unroll
+        for (int c = 0; c < 28; c++) {
+            b[4 * c] = (uint8_t) o[c]; b[4 * c + 1] = (uint8_t) (o[c] >> 8);
+            b[4 * c + 2] = (uint8_t) (o[c] >> 16); b[4 * c + 3] = (uint8_t) (o[c] >> 24);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 12; j++) { X[j] = 0; o[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 20; j++) S[j] = 0;
+}
+
+enum { AL_VERIFY = AL_AUX, AL_OFFERED12 = AL_TRAFFIC };
+
+struct Tls12FinishedArgs {
+    const tlsrec_tls12_conn *conns;       /* master only */
+    const tlsrec_tls13_secret *transcripts;
+    const uint8_t *offered;               /* 16 bytes per connection, 12 compared; with match, or both NULL */
+    uint8_t *verify;                      /* 16 bytes per connection; may be NULL */
+    uint32_t *match;
+    uint32_t count, aligned, l0, l1;      /* l0, l1: "clie" "nt f" or "serv" "er f" */
+};
+
+template <class T> __global__ void __launch_bounds__(64) tls12_finished_kernel(Tls12FinishedArgs a)
+{
+    typedef typename T::W W;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.count) return;
+    W ip[8], op[8];
+    /* every load is issued before the first compression */
+    uint32_t Hs[T::HC], S[20], X[3], O[3] = { 0u, 0u, 0u };
+    load_cells<T::HC>(a.transcripts[i].secret, (a.aligned & AL_TRANSCRIPT) != 0, Hs);
+    if (a.match) load_cells<3>(a.offered + 16 * (size_t) i, (a.aligned & AL_OFFERED12) != 0, O);
+    {
+        uint32_t M[12];
+        W kb[16];
+        load_cells<12>(reinterpret_cast<const uint8_t *>(a.conns + i), (a.aligned & AL_CONNS) != 0, M);
+        key_block<T, 12, false>(kb, M, 48, 0);
+#pragma unroll
+        for (int j = 0; j < 12; j++) M[j] = 0;
+        hmac_mid_block<T>(kb, ip, op);
+    }
+    S[0] = a.l0;
+    S[1] = a.l1;
+    S[2] = 0x696e6973u;          /* "inis" */
+    S[3] = 0x68656400u | (Hs[0] >> 24);         /* "hed" */
+#pragma unroll
+    for (int k = 1; k < T::HC; k++) S[3 + k] = (Hs[k - 1] << 8) | (Hs[k] >> 24);
+    S[3 + T::HC] = Hs[T::HC - 1] << 8;
+#pragma unroll
+    for (int k = 4 + T::HC; k < 20; k++) S[k] = 0;
+    tls12_p_hash<T, 15 + (int) T::HB, 3>(ip, op, S, X);
+    if (a.verify) {
+        uint8_t *b = a.verify + 16 * (size_t) i;
+        if (a.aligned & AL_VERIFY) {
+            *reinterpret_cast<uint4 *>(b) = make_uint4(__builtin_bswap32(X[0]), __builtin_bswap32(X[1]),
+                                                       __builtin_bswap32(X[2]), 0u);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const uint32_t v = c < 3 ? X[c] : 0u;
+                b[4 * c] = (uint8_t) (v >> 24); b[4 * c + 1] = (uint8_t) (v >> 16);
+                b[4 * c + 2] = (uint8_t) (v >> 8); b[4 * c + 3] = (uint8_t) v;
+            }
+        }
+    }
+    if (a.match) {
+        /* mbedtls_ct_memcmp over 12 bytes: the OR of the XOR of the three cells, no early exit, no branch on the data */
+        const uint32_t d = (X[0] ^ O[0]) | (X[1] ^ O[1]) | (X[2] ^ O[2]);
+        a.match[i] = d == 0 ? 1u : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) X[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ip[j] = 0; op[j] = 0; }
+#pragma unroll
+    for (int j = 0; j < 20; j++) S[j] = 0;
+}
+
 } /* namespace tlsks */
 
 using namespace tlsks;
@@ -2546,4 +2861,78 @@ extern "C" int tlsrec_tls12_keytab_derive_cbc(tlsrec_keytab *kt, uint32_t first,
     if (r == 0 && count)
         r = tlsrec__keytab_commit_staged_cbc(kt, first, 2 * count, cipher, mac, etm, (hipStream_t) stream);
     return r;
+}
+
+/* ---- the handshake before the key expansion: master secret, Finished ---- */
+extern "C" int tlsrec_tls12_calc_finished(int prf, const unsigned char master[48], const unsigned char *transcript_hash,
+                                          int from, unsigned char out[12])
+{
+    const int a = prf_index(prf);
+    if (a < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (from != TLSREC_IS_CLIENT && from != TLSREC_IS_SERVER) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (!master || !transcript_hash || !out) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    /* ssl_tls.c:7217-7219, :7252 */
+    const char *lbl = from == TLSREC_IS_CLIENT ? "client finished" : "server finished";
+    return prf_run(a, master, 48, lbl, 15, transcript_hash, alg_len(a), nullptr, 0, out, 12);
+}
+
+template <class T, bool EMS> static hipError_t tls12_launch_master(const Tls12MasterArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL((tls12_master_kernel<T, EMS>), dim3((a.count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+extern "C" int tlsrec_tls12_batch_compute_master(int prf, uint32_t pms_len, int extended_ms,
+                                                 const tlsrec_tls12_pms_conn *conns, tlsrec_tls12_conn *out,
+                                                 uint32_t count, void *stream)
+{
+    const int alg = prf_index(prf);
+    if (alg < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if ((!conns || !out) && count) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (pms_len == 0) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (pms_len > sizeof(conns->premaster)) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (count == 0) return 0;
+    static const int device = tlsrec_device_check();     /* no key table vouches for a device here; asked once */
+    if (device != 0) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    Tls12MasterArgs a;
+    a.conns = conns;
+    a.out = out;
+    a.count = count;
+    a.pms_len = pms_len;
+    a.aligned = al(conns, AL_CONNS) | al(out, AL_AUX);     /* 240- and 112-byte records */
+    hipStream_t st = (hipStream_t) stream;
+    hipError_t e;
+    if (alg == H_SHA384) e = extended_ms ? tls12_launch_master<L384, true>(a, st) : tls12_launch_master<L384, false>(a, st);
+    else e = extended_ms ? tls12_launch_master<L256, true>(a, st) : tls12_launch_master<L256, false>(a, st);
+    return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+}
+
+extern "C" int tlsrec_tls12_batch_verify_data(int prf, int from, const tlsrec_tls12_conn *conns,
+                                              const tlsrec_tls13_secret *transcripts, const uint8_t *offered,
+                                              uint8_t *verify, uint32_t *match, uint32_t count, void *stream)
+{
+    const int alg = prf_index(prf);
+    if (alg < 0) return TLSREC_ERR_SSL_FEATURE_UNAVAILABLE;
+    if (from != TLSREC_IS_CLIENT && from != TLSREC_IS_SERVER) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if ((!conns || !transcripts) && count) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if ((offered == nullptr) != (match == nullptr)) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (!verify && !match && count) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (count == 0) return 0;
+    static const int device = tlsrec_device_check();
+    if (device != 0) return TLSREC_ERR_SSL_HW_ACCEL_FAILED;
+    Tls12FinishedArgs a;
+    a.conns = conns;
+    a.transcripts = transcripts;
+    a.offered = offered;
+    a.verify = verify;
+    a.match = match;
+    a.count = count;
+    a.aligned = al(conns, AL_CONNS) | al(transcripts, AL_TRANSCRIPT) | al(offered, AL_OFFERED12) | al(verify, AL_VERIFY);
+    /* "client finished" / "server finished" (ssl_tls.c:7217-7219): the first two cells differ */
+    a.l0 = from == TLSREC_IS_CLIENT ? 0x636c6965u : 0x73657276u;
+    a.l1 = from == TLSREC_IS_CLIENT ? 0x6e742066u : 0x65722066u;
+    hipStream_t st = (hipStream_t) stream;
+    if (alg == H_SHA384) hipLaunchKernelGGL(tls12_finished_kernel<L384>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(tls12_finished_kernel<L256>, dim3((count + 63) / 64), dim3(64), 0, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED;
 }

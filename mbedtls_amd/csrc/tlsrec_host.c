@@ -393,3 +393,27 @@ int tlsrec_shard_bounds(uint64_t n_records, uint32_t rank, uint32_t world, uint6
     *count = base + (rank < extra ? 1u : 0u);
     return 0;
 }
+
+/* The premaster of the PSK key exchanges, RFC 4279 section 2 (PSA's PSK_TO_MS,
+ * ssl_tls.c:6307-6366): uint16 len || other || uint16 len || psk; for plain PSK
+ * the other secret is psk_len zero bytes. */
+int tlsrec_tls12_psk_premaster(const unsigned char *other, size_t other_len, const unsigned char *psk, size_t psk_len,
+                               unsigned char *out, size_t out_size, size_t *olen)
+{
+    if (!psk || !out || !olen || psk_len == 0) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (!other && other_len) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    const size_t ol = other ? other_len : psk_len;
+    if (ol > 65535 || psk_len > 65535) return TLSREC_ERR_SSL_BAD_INPUT_DATA;
+    if (out_size < 4 + ol + psk_len) return TLSREC_ERR_SSL_BUFFER_TOO_SMALL;
+    unsigned char *p = out;
+    *p++ = (unsigned char) (ol >> 8);
+    *p++ = (unsigned char) ol;
+    if (other) memcpy(p, other, ol);
+    else memset(p, 0, ol);
+    p += ol;
+    *p++ = (unsigned char) (psk_len >> 8);
+    *p++ = (unsigned char) psk_len;
+    memcpy(p, psk, psk_len);
+    *olen = 4 + ol + psk_len;
+    return 0;
+}

@@ -9,6 +9,10 @@ reference functions; the PRF (RFC 5246 section 5) runs in HIP kernels.
     mbedtls_ssl_tls12_export_keying_material  (:8886)  -> tls12_export_keying_material
     batch: master secrets in HBM -> key-table slots    -> tls12_keytab_derive
     the same for the AES-CBC + HMAC suites             -> tls12_keytab_derive_cbc
+    batch: ssl_compute_master                 (:6251)  -> tls12_batch_compute_master
+    ssl_calc_finished_tls_generic             (:7209)  -> tls12_calc_finished
+    batch: the same + the check of parse_finished (:7530) -> tls12_batch_verify_data
+    the RFC 4279 premaster of the PSK exchanges (:6307) -> tls12_psk_premaster (host only)
 
 `prf` is explicit (TLS 1.2 fixes the hash per suite, not per cipher); errors
 raise KeyScheduleError with the reference's code.
@@ -27,10 +31,13 @@ PRF_SHA256 = _abi.TLS_PRF_SHA256
 IS_CLIENT = _abi.IS_CLIENT
 IS_SERVER = _abi.IS_SERVER
 CONN_BYTES = ctypes.sizeof(_abi.CTls12Conn)      # master[48] || server_random[32] || client_random[32]
+PMS_CONN_BYTES = ctypes.sizeof(_abi.CTls12PmsConn)   # premaster[128] || client_random[32] || server_random[32] || session_hash[48]
 
-__all__ = ["PRF_NONE", "PRF_SHA384", "PRF_SHA256", "IS_CLIENT", "IS_SERVER", "CONN_BYTES", "KeyScheduleError",
+__all__ = ["PRF_NONE", "PRF_SHA384", "PRF_SHA256", "IS_CLIENT", "IS_SERVER", "CONN_BYTES", "PMS_CONN_BYTES",
+           "KeyScheduleError",
            "tls_prf", "tls12_compute_master", "tls12_split_key_block", "tls12_make_keys",
-           "tls12_export_keying_material", "tls12_keytab_derive", "tls12_keytab_derive_cbc", "tls12_slots"]
+           "tls12_export_keying_material", "tls12_keytab_derive", "tls12_keytab_derive_cbc", "tls12_slots",
+           "tls12_batch_compute_master", "tls12_batch_verify_data", "tls12_calc_finished", "tls12_psk_premaster"]
 
 
 def _key_set(ks):
@@ -111,3 +118,44 @@ def tls12_slots(first: int, i: int, endpoint: int):
     the reverse."""
     c, s = first + 2 * i, first + 2 * i + 1
     return (s, c) if endpoint == IS_SERVER else (c, s)
+
+
+def tls12_batch_compute_master(prf: int, pms_len: int, extended_ms: bool, conns, out, count: int, stream=None) -> None:
+    """`conns`: device buffer of count x 240 bytes (tlsrec_tls12_pms_conn), only
+    read; `out`: device buffer of count x 112 bytes, which receives master ||
+    server_random || client_random per connection -- the `conns` of
+    tls12_keytab_derive / _derive_cbc / tls12_batch_verify_data on the same stream."""
+    _chk("tlsrec_tls12_batch_compute_master", _abi.load().tlsrec_tls12_batch_compute_master(
+        prf, pms_len, int(bool(extended_ms)), _ptr(conns), _ptr(out), count, _stream(stream)))
+
+
+def tls12_calc_finished(prf: int, master: bytes, transcript_hash: bytes, from_: int) -> bytes:
+    """verify_data (12 bytes) of the Finished message sent by `from_` (IS_CLIENT / IS_SERVER)."""
+    need = 48 if prf == PRF_SHA384 else 32
+    if len(master) != 48 or (prf in (PRF_SHA256, PRF_SHA384) and len(transcript_hash) != need):
+        raise KeyScheduleError("tlsrec_tls12_calc_finished", _abi.ERR_SSL_BAD_INPUT_DATA)
+    out = ctypes.create_string_buffer(12)
+    _chk("tlsrec_tls12_calc_finished", _abi.load().tlsrec_tls12_calc_finished(
+        prf, _b(master), _b(transcript_hash), from_, out))
+    return out.raw
+
+
+def tls12_batch_verify_data(prf: int, from_: int, conns, transcripts, offered, verify, match, count: int,
+                            stream=None) -> None:
+    """`conns`: count x 112 bytes (only master is read); `transcripts`: count x 48
+    bytes; `offered` / `verify`: count x 16 bytes, 12 used; `match`: count uint32.
+    offered and match are both given or both None; verify may be None only with match."""
+    _chk("tlsrec_tls12_batch_verify_data", _abi.load().tlsrec_tls12_batch_verify_data(
+        prf, from_, _ptr(conns), _ptr(transcripts), _ptr(offered), _ptr(verify), _ptr(match), count, _stream(stream)))
+
+
+def tls12_psk_premaster(psk: bytes, other: bytes | None = None, out_size: int | None = None) -> bytes:
+    """uint16 len || other || uint16 len || psk (RFC 4279 section 2); other None = plain
+    PSK (len(psk) zero bytes).  Needs no GPU."""
+    ol = len(other) if other is not None else len(psk)
+    size = 4 + ol + len(psk) if out_size is None else out_size
+    out = ctypes.create_string_buffer(max(1, size))
+    olen = ctypes.c_size_t(0)
+    _chk("tlsrec_tls12_psk_premaster", _abi.load().tlsrec_tls12_psk_premaster(
+        _b(other), len(other) if other is not None else 0, _b(psk), len(psk), out, size, ctypes.byref(olen)))
+    return out.raw[:olen.value]

@@ -37,6 +37,15 @@ connections (create_psk_binder + derive_early_secrets + make_traffic_keys per
 connection, then one tlsrec_keytab_load), and the handshake-stage derive kernel
 under the same hash for the ns-per-compression yardstick.
 
+--tls12-handshake: the TLS 1.2 / DTLS 1.2 handshake batches over 64 K connections
+of one (prf, pms_len, extended_ms): (a) tlsrec_tls12_batch_compute_master, (b) the
+chain compute_master -> tlsrec_tls12_keytab_derive (AES-128-GCM under SHA-256,
+AES-256-GCM under SHA-384) as one enqueue, (c) tlsrec_tls12_batch_verify_data
+with offered values, (d) the host path they replace on at most 2 048
+connections (tlsrec_tls12_compute_master + tlsrec_tls12_calc_finished per
+connection), and (e) the tlsrec_tls12_keytab_derive AES-128-GCM derive kernel
+under the same hash for the ns-per-compression yardstick.
+
 Prints one JSON line; the whole call and the derive kernel alone are timed
 with HIP events on the call's stream, the key-setup kernel is the difference.
 
@@ -45,6 +54,7 @@ with HIP events on the call's stream, the key-setup kernel is the difference.
     python tools/bench_keysched.py --tls12 --cbc-mac 2 [--etm] [--count 65536]
     python tools/bench_keysched.py --tls13-handshake [--cipher 1|2] [--psk-len 32] [--shared-len 32]
     python tools/bench_keysched.py --tls13-early [--cipher 1|2|3] [--psk-len 32] [--no-keys]
+    python tools/bench_keysched.py --tls12-handshake [--prf sha256|sha384] [--pms-len 32] [--ems]
 """
 import argparse
 import ctypes
@@ -568,8 +578,124 @@ def main_tls13_early(a):
                                     "builds are not counted", "tls13 early stage" + (" + key setup" if keys else ""))}))
 
 
+def master_compressions(hname, pms_len, ems):
+    """SHA-2 compressions per connection of tls12_master_kernel"""
+    if hname == "sha384":
+        return 7
+    return (12 if ems else 13) + (0 if pms_len <= 64 else 2 if pms_len <= 119 else 3)
+
+
+def host_tls12_handshake_leg(prf, hname, pms_len, ems, raw, traw, n):
+    """tlsrec_tls12_compute_master + tlsrec_tls12_calc_finished per connection: two synchronised round trips"""
+    from mbedtls_amd import tls12 as T
+    hl = 48 if hname == "sha384" else 32
+
+    def one(i):
+        c = raw[240 * i:240 * i + 240]
+        m = T.tls12_compute_master(prf, c[:pms_len], c[192:192 + hl] if ems else c[128:192], ems)
+        return T.tls12_calc_finished(prf, m, traw[48 * i:48 * i + hl], T.IS_CLIENT)
+
+    one(0)
+    t0 = time.perf_counter()
+    for i in range(n):
+        one(i)
+    dt = time.perf_counter() - t0
+    return {"value": round(n / dt), "unit": "connections/s", "kind": "single-shot", "leg": "host_path",
+            "seconds": round(dt, 4),
+            "sample": f"{n} connections: tlsrec_tls12_compute_master + tlsrec_tls12_calc_finished each; wall time"}
+
+
+def main_tls12_handshake(a):
+    """the two handshake batches, their chain into the key expansion, the host path they replace, and the
+    key-expansion derive kernel of the same run under the same hash as the ns-per-compression yardstick"""
+    from tools import rowlib
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import tls12 as T
+    from mbedtls_amd.batch import _ptr, _stream
+    from tests.prng import prng_array
+    dev = torch.device("cuda")
+    L = M.load()
+    vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+    L.tlsrec__tls12_stage_keys.restype = ci
+    L.tlsrec__tls12_stage_keys.argtypes = [vp, u32, u32, ci, ci, vp, vp]
+    hname, n, pl, ems = a.prf, a.count, a.pms_len, bool(a.ems)
+    sha384 = hname == "sha384"
+    prf = T.PRF_SHA384 if sha384 else T.PRF_SHA256
+    cipher = M.CIPHER_AES_256_GCM if sha384 else M.CIPHER_AES_128_GCM
+    raw = prng_array(0x7158, n * 240)
+    traw = prng_array(0x7159, n * 48)
+    conns = torch.from_numpy(raw).to(dev)
+    trs = torch.from_numpy(traw).to(dev)
+    out = torch.zeros(n * 112, dtype=torch.uint8, device=dev)
+    off = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    vd = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    mt = torch.zeros(n, dtype=torch.int32, device=dev)
+    kt, kty = M.KeyTable(2 * n), M.KeyTable(2 * n)
+
+    def ok(r):
+        assert r == 0, r
+
+    def chain():
+        T.tls12_batch_compute_master(prf, pl, ems, conns, out, n)
+        T.tls12_keytab_derive(kt, 0, n, cipher, prf, out)
+
+    s = _stream(None)
+    T.tls12_batch_compute_master(prf, pl, ems, conns, out, n)
+    T.tls12_batch_verify_data(prf, T.IS_CLIENT, out, trs, None, off, None, n)     # the offered values are the right ones
+    legs = {
+        "master": lambda: T.tls12_batch_compute_master(prf, pl, ems, conns, out, n),
+        "chain": chain,
+        "derive_call": lambda: T.tls12_keytab_derive(kt, 0, n, cipher, prf, out),
+        "verify_data": lambda: T.tls12_batch_verify_data(prf, T.IS_CLIENT, out, trs, off, vd, mt, n),
+        "stage_keys_aes128": lambda: ok(L.tlsrec__tls12_stage_keys(kty.handle, 0, n, M.CIPHER_AES_128_GCM, prf,
+                                                                   _ptr(out), s)),
+    }
+    ms_, wall = {}, {}
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()
+        ms_[name], wall[name] = rowlib.event_timed(fn, a.steps)
+    assert int(mt.sum().item()) == n
+    # the AES-128-GCM key block is 40 bytes: 2 P_SHA256 iterations (5n + 3 = 13), 1 P_SHA384 iteration (5n + 2 = 7)
+    comp = {"master": master_compressions(hname, pl, ems), "verify_data": 6 if sha384 else 7,
+            "stage_keys_aes128": 7 if sha384 else 13}
+    ns = {k: ms_[k] * 1e6 / n / comp[k] for k in comp}
+    nh = min(2048, n)
+    host = None if a.no_cpu else host_tls12_handshake_leg(prf, hname, pl, ems, raw.tobytes()[:240 * nh],
+                                                          traw.tobytes()[:48 * nh], nh)
+    cps = {k: n / (ms_[k] / 1e3) for k in ("master", "chain", "verify_data")}
+    print(json.dumps({
+        "metric": "TLS 1.2 master secrets derived per second", "value": round(cps["master"]), "unit": "connections/s",
+        "count": n, "hash": hname, "pms_len": pl, "extended_ms": int(ems), "call": "tlsrec_tls12_batch_compute_master",
+        "ms_per_batch_events": round(ms_["master"], 4), "ms_per_batch_wall": round(wall["master"] * 1e3, 4),
+        "compressions_per_connection": comp["master"], "ns_per_compression": round(ns["master"], 4),
+        "per_compression_vs_stage_keys_same_run": round(ns["master"] / ns["stage_keys_aes128"], 3),
+        "chain": {"calls": "tlsrec_tls12_batch_compute_master -> tlsrec_tls12_keytab_derive", "cipher": cipher,
+                  "slots": 2 * n, "connections_per_s": round(cps["chain"]), "ms": round(ms_["chain"], 4),
+                  "ms_wall": round(wall["chain"] * 1e3, 4), "keytab_derive_alone_ms": round(ms_["derive_call"], 4)},
+        "batch_verify_data": {"connections_per_s": round(cps["verify_data"]), "ms": round(ms_["verify_data"], 4),
+                              "compressions_per_connection": comp["verify_data"],
+                              "ns_per_compression": round(ns["verify_data"], 4),
+                              "per_compression_vs_stage_keys_same_run":
+                                  round(ns["verify_data"] / ns["stage_keys_aes128"], 3)},
+        "stage_keys_same_run": {"cipher": M.CIPHER_AES_128_GCM, "derive_kernel_ms": round(ms_["stage_keys_aes128"], 4),
+                                "compressions_per_connection": comp["stage_keys_aes128"],
+                                "derive_kernel_ns_per_compression": round(ns["stage_keys_aes128"], 4)},
+        "host_path": host, "speedup_vs_host_path": round(min(cps["master"], cps["verify_data"]) / host["value"], 1)
+        if host else None,
+        "roofline": rowlib.roofline((16 * ((pl + 15) // 16) + 64 + (48 if ems else 0) + 112) * n, ms_["master"],
+                                    "per connection: the premaster's 16-byte groups, the 64 random bytes and with "
+                                    "extended_ms the session hash read, the 112-byte tlsrec_tls12_conn written",
+                                    "tls12 master secret")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tls12-handshake", action="store_true",
+                    help="the TLS 1.2 handshake batches (tlsrec_tls12_batch_compute_master, _batch_verify_data)")
+    ap.add_argument("--pms-len", type=int, default=32, help="--tls12-handshake: 1..128")
+    ap.add_argument("--ems", action="store_true", help="--tls12-handshake: extended master secret (RFC 7627)")
     ap.add_argument("--tls13-early", action="store_true",
                     help="the resumed-handshake batches (tlsrec_tls13_keytab_derive_early, _batch_psk_binder, "
                          "_batch_ticket_psk)")
@@ -591,6 +717,9 @@ def main():
                     help="--tls12: an AES-CBC + HMAC suite (1 SHA-1, 2 SHA-256, 3 SHA-384), tlsrec_tls12_keytab_derive_cbc")
     ap.add_argument("--etm", action="store_true", help="--cbc-mac: encrypt-then-MAC slots")
     a = ap.parse_args()
+    if a.tls12_handshake:
+        a.prf = a.prf or "sha256"
+        return main_tls12_handshake(a)
     if a.tls13_early:
         a.cipher = 1 if a.cipher is None else a.cipher
         return main_tls13_early(a)

@@ -1162,6 +1162,101 @@ int tlsrec_ticket_write(const tlsrec_keytab *kt, const tlsrec_ticket_keys *keys,
 int tlsrec_ticket_parse(const tlsrec_keytab *kt, const tlsrec_ticket_keys *keys, const tlsrec_ticket *tickets,
                         uint32_t n, uint8_t *arena, tlsrec_ticket_res *res, void *stream);
 
+/* ---- DTLS cookies (library/ssl_cookie.c, RFC 6347 4.2.1) ------------------
+ * The stateless cookie exchange of a DTLS server for a batch of first-flight
+ * datagrams: mbedtls_ssl_cookie_write / mbedtls_ssl_cookie_check
+ * (ssl_cookie.c:117-179, :184-250) and mbedtls_ssl_check_dtls_clihlo_cookie
+ * (ssl_msg.c:3322-3454), one item per lane, all under one secret.
+ *     cookie = BE32(time) || HMAC-SHA256(key, BE32(time) || cli_id)[0..28)
+ * (ssl_cookie.c:140-169).  HMAC-SHA256 truncated to 28 bytes is the only MAC:
+ * the reference picks SHA-256 whenever it is compiled in (COOKIE_MD,
+ * ssl_cookie.c:40-48; SHA-384 only in a build without it). */
+#define TLSREC_ERR_SSL_DECODE_ERROR           (-0x7300)  /* ssl.h:48 */
+#define TLSREC_ERR_SSL_HELLO_VERIFY_REQUIRED  (-0x6A80)  /* ssl.h:123 */
+#define TLSREC_COOKIE_TIMEOUT 60                         /* MBEDTLS_SSL_COOKIE_TIMEOUT, ssl_cookie.h:27 */
+#define TLSREC_COOKIE_LEN 32                             /* COOKIE_LEN = 4 + COOKIE_HMAC_LEN, ssl_cookie.c:56 */
+#define TLSREC_DTLS_HVR_LEN 60                           /* 28 + TLSREC_COOKIE_LEN */
+
+/* mbedtls_ssl_cookie_ctx (ssl_cookie.h:39-48): the two HMAC midstates of the
+ * key (device memory; the raw key is not kept) and the timeout. */
+typedef struct tlsrec_cookie_ctx tlsrec_cookie_ctx;   /* opaque */
+
+/* mbedtls_ssl_cookie_init + _setup (ssl_cookie.c:58-111).  key == NULL: 32
+ * bytes of getrandom(2), as psa_generate_key there; a caller's key is for
+ * tests and for servers that share one secret.  timeout: seconds a cookie
+ * stays valid, 0 = never expires (ssl_cookie.c:239).  HW_ACCEL_FAILED without
+ * a usable device. */
+int  tlsrec_cookie_setup(tlsrec_cookie_ctx **ctx, const unsigned char key[32], uint32_t timeout);
+/* mbedtls_ssl_cookie_set_timeout (ssl_cookie.c:68-71) */
+void tlsrec_cookie_set_timeout(tlsrec_cookie_ctx *ctx, uint32_t delay);
+/* mbedtls_ssl_cookie_free (ssl_cookie.c:73-82): zeroes the device and host copies, then releases them; NULL is fine */
+void tlsrec_cookie_free(tlsrec_cookie_ctx *ctx);
+
+typedef struct tlsrec_cookie_item {
+    uint64_t id_off;      /* client transport id (ssl->cli_id) in id_arena */
+    uint64_t cookie_off;  /* write: 32 bytes of space; check: the received cookie, in cookie_arena */
+    uint32_t id_len;      /* <= 255 */
+    uint32_t cookie_len;  /* write: space (>= 32); check: received length */
+} tlsrec_cookie_item;
+
+/* f_cookie_write / f_cookie_check for n clients; every pointer but ctx is a
+ * device pointer, offsets may be unaligned, `now` is the caller's
+ * mbedtls_time(NULL).  status[i]:
+ *   write: 0; BAD_INPUT_DATA for id_len > 255; BUFFER_TOO_SMALL for a space
+ *          under 32 bytes (MBEDTLS_SSL_CHK_BUF_PTR, ssl_cookie.c:132), nothing written;
+ *   check, in the order of ssl_cookie.c:194-242: BAD_INPUT_DATA for
+ *          id_len > 255; -1 for cookie_len != 32; INVALID_MAC for a MAC
+ *          mismatch (PSA_ERROR_INVALID_SIGNATURE through psa_to_ssl_errors,
+ *          ssl_tls.c:2157-2166; compared in constant time); -1 when
+ *          timeout != 0 && now - cookie_time > timeout (64-bit unsigned, the
+ *          unsigned long of LP64: a cookie from the future is rejected); else 0.
+ * A status the kernel did not reach reads INTERNAL_ERROR.  n == 0: 0, no launch. */
+int tlsrec_cookie_batch_write(const tlsrec_cookie_ctx *ctx, uint64_t now, const tlsrec_cookie_item *items, uint32_t n,
+                              const uint8_t *id_arena, uint8_t *cookie_arena, int32_t *status, void *stream);
+int tlsrec_cookie_batch_check(const tlsrec_cookie_ctx *ctx, uint64_t now, const tlsrec_cookie_item *items, uint32_t n,
+                              const uint8_t *id_arena, const uint8_t *cookie_arena, int32_t *status, void *stream);
+
+/* The same for one client in host buffers, with time(NULL): the callback
+ * types of mbedtls_ssl_conf_dtls_cookies (ssl.h:2935), so
+ *     mbedtls_ssl_conf_dtls_cookies(conf, tlsrec_cookie_write, tlsrec_cookie_check, ctx)
+ * works.  NULL ctx or cli_id: BAD_INPUT_DATA.  write advances *p by 32 on success. */
+int tlsrec_cookie_write(void *ctx, unsigned char **p, unsigned char *end, const unsigned char *cli_id,
+                        size_t cli_id_len);
+int tlsrec_cookie_check(void *ctx, const unsigned char *cookie, size_t cookie_len, const unsigned char *cli_id,
+                        size_t cli_id_len);
+
+typedef struct tlsrec_clihlo {
+    uint64_t off;       /* the datagram (record + handshake headers included) in `arena` */
+    uint64_t id_off;    /* cli_id in `id_arena` */
+    uint64_t out_off;   /* obuf in `out_arena` */
+    uint32_t len;       /* in_len */
+    uint32_t id_len;    /* <= 255 */
+    uint32_t out_cap;   /* buf_len */
+    uint32_t reserved;
+} tlsrec_clihlo;
+
+typedef struct tlsrec_clihlo_res { int32_t status; uint32_t olen; } tlsrec_clihlo_res;
+
+/* mbedtls_ssl_check_dtls_clihlo_cookie (ssl_msg.c:3322-3454) for n datagrams
+ * in one launch: parse, check the embedded cookie, write the
+ * HelloVerifyRequest where it fails.  res[i].status:
+ *   DECODE_ERROR            len < 61, in[0] != 22, epoch != 0, fragment_offset != 0,
+ *                           61 + sid_len > len or 61 + sid_len + cookie_len > len (:3360-3393);
+ *   0                       the cookie passes tlsrec_cookie_batch_check; olen = 0, nothing written;
+ *   BUFFER_TOO_SMALL        it fails and out_cap < 28 (:3424);
+ *   INTERNAL_ERROR          it fails and 28 <= out_cap < 60: f_cookie_write fails its buffer check
+ *                           (:3436-3440); this call writes nothing then;
+ *   HELLO_VERIFY_REQUIRED   otherwise: olen = 60 and the datagram of :3429-3451 at out_off -- bytes
+ *                           0-24 of the input, msg_type 3, lengths 47 / 35 / 35, FE FF, 32 and
+ *                           a fresh cookie stamped `now`.
+ * An id_len > 255 makes both callbacks fail: after the DECODE_ERROR checks,
+ * BUFFER_TOO_SMALL or INTERNAL_ERROR by out_cap alone.  Nothing outside
+ * [out_off, out_off + 60) is written, and that only with HELLO_VERIFY_REQUIRED.
+ * A result the kernel did not reach reads INTERNAL_ERROR, olen 0. */
+int tlsrec_dtls_check_clihlo_cookies(const tlsrec_cookie_ctx *ctx, uint64_t now, const tlsrec_clihlo *hellos, uint32_t n,
+                                     const uint8_t *arena, const uint8_t *id_arena, uint8_t *out_arena,
+                                     tlsrec_clihlo_res *res, void *stream);
+
 /* ---- engine ------------------------------------------------------------- */
 /* 0 if a gfx950 device is usable, else TLSREC_ERR_SSL_HW_ACCEL_FAILED. */
 int tlsrec_device_check(void);

@@ -18,7 +18,8 @@ from ._abi import (CIPHER_AES_128_GCM, CIPHER_AES_256_GCM, CIPHER_CHACHA20_POLY1
                    CID_LEN_MAX, VERSION_TLS1_2, VERSION_TLS1_3, ERR_SSL_COUNTER_WRAPPING,
                    ERR_SSL_UNEXPECTED_RECORD, ERR_SSL_EARLY_MESSAGE, ERR_SSL_CONN_EOF, DTLS_MAX_DATAGRAM,
                    DTLS_OUT_BUFFER_LEN, DTLS_DROPPED, DTLS_NOT_REACHED, DTLS_ANTI_REPLAY,
-                   DTLS_IGNORE_UNEXPECTED_CID,
+                   DTLS_IGNORE_UNEXPECTED_CID, ERR_SSL_DECODE_ERROR, ERR_SSL_HELLO_VERIFY_REQUIRED,
+                   COOKIE_TIMEOUT, COOKIE_LEN, DTLS_HVR_LEN, COOKIE_ITEM, CLIHLO, CLIHLO_RES,
                    BATCH_REC, BATCH_RES, KEY_MATERIAL, load)
 from .batch import (KeyTable, batch_decrypt, batch_encrypt, frame_check, host_batch, key_material,  # noqa: F401
                     records, results, seq_bytes)
@@ -26,6 +27,8 @@ from .record import Record, Transform, decrypt_buf, encrypt_buf  # noqa: F401
 from .shard import Shard, broadcast_keys, reduce_status, shard_bounds, status_counts  # noqa: F401
 from . import cbc  # noqa: F401
 from . import tls12  # noqa: F401
+from . import cookie  # noqa: F401
+from .cookie import CookieContext  # noqa: F401
 from .tls12 import (tls_prf, tls12_compute_master, tls12_split_key_block, tls12_make_keys,  # noqa: F401
                     tls12_export_keying_material, tls12_keytab_derive, tls12_slots)
 

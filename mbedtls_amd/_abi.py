@@ -29,6 +29,9 @@ ERR_SSL_SESSION_TICKET_EXPIRED = -0x6D80
 ERR_SSL_UNEXPECTED_RECORD = -0x6700
 ERR_SSL_EARLY_MESSAGE = -0x6480
 ERR_SSL_CONN_EOF = -0x7280
+ERR_SSL_DECODE_ERROR = -0x7300
+ERR_SSL_HELLO_VERIFY_REQUIRED = -0x6A80
+COOKIE_TIMEOUT, COOKIE_LEN, DTLS_HVR_LEN = 60, 32, 60
 DTLS_MAX_DATAGRAM = 16477
 DTLS_OUT_BUFFER_LEN = 16477
 DTLS_DROPPED, DTLS_NOT_REACHED = 1, 2
@@ -95,6 +98,11 @@ STREAM_OUT_RES = np.dtype([("status", "<i4"), ("first", "<u4"), ("nrec", "<u4"),
 TICKET = np.dtype([("off", "<u8"), ("len", "<u4"), ("clear_len", "<u4")])
 TICKET_RES = np.dtype([("status", "<i4"), ("tlen", "<u4"), ("reserved", "<u4", 2)])
 assert TICKET.itemsize == 16 and TICKET_RES.itemsize == 16
+COOKIE_ITEM = np.dtype([("id_off", "<u8"), ("cookie_off", "<u8"), ("id_len", "<u4"), ("cookie_len", "<u4")])
+CLIHLO = np.dtype([("off", "<u8"), ("id_off", "<u8"), ("out_off", "<u8"), ("len", "<u4"), ("id_len", "<u4"),
+                   ("out_cap", "<u4"), ("reserved", "<u4")])
+CLIHLO_RES = np.dtype([("status", "<i4"), ("olen", "<u4")])
+assert COOKIE_ITEM.itemsize == 24 and CLIHLO.itemsize == 40 and CLIHLO_RES.itemsize == 8
 STREAM_READ_REQ = np.dtype([("out_off", "<u8"), ("out_cap", "<u4"), ("reserved", "<u4")])
 STREAM_READ_RES = np.dtype([("copied", "<u4"), ("records", "<u4"), ("left", "<u4"), ("reserved", "<u4")])
 assert STREAM_READ_REQ.itemsize == 16 and STREAM_READ_RES.itemsize == 16
@@ -322,6 +330,14 @@ SIGNATURES = {
     "tlsrec_tls12_psk_premaster": (_INT, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _VP]),
     "tlsrec_ticket_write": (_INT, [_VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_ticket_parse": (_INT, [_VP, _VP, _VP, _U32, _VP, _VP, _VP]),
+    "tlsrec_cookie_setup": (_INT, [ctypes.POINTER(_VP), _VP, _U32]),
+    "tlsrec_cookie_set_timeout": (None, [_VP, _U32]),
+    "tlsrec_cookie_free": (None, [_VP]),
+    "tlsrec_cookie_batch_write": (_INT, [_VP, ctypes.c_uint64, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "tlsrec_cookie_batch_check": (_INT, [_VP, ctypes.c_uint64, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "tlsrec_cookie_write": (_INT, [_VP, ctypes.POINTER(_VP), _VP, _VP, _SZ]),
+    "tlsrec_cookie_check": (_INT, [_VP, _VP, _SZ, _VP, _SZ]),
+    "tlsrec_dtls_check_clihlo_cookies": (_INT, [_VP, ctypes.c_uint64, _VP, _U32, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_stream_decrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_stream_read": (_INT, [_VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_stream_out_size": (ctypes.c_uint64, [_INT, _INT, _U32, ctypes.c_uint64, _U32]),

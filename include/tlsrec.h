@@ -1257,6 +1257,98 @@ int tlsrec_dtls_check_clihlo_cookies(const tlsrec_cookie_ctx *ctx, uint64_t now,
                                      const uint8_t *arena, const uint8_t *id_arena, uint8_t *out_arena,
                                      tlsrec_clihlo_res *res, void *stream);
 
+/* ---- handshake transcripts (library/ssl_tls.c, ssl_tls13_generic.c) -------
+ * The running handshake hash of many connections, kept in device memory and
+ * advanced in batches; its digests land in the fields the batch calls above
+ * read, so no transcript byte goes through the host between two of them.
+ *
+ *   reference                                              here
+ *   ssl->handshake->fin_sha256_psa / fin_sha384_psa        tlsrec_transcript_state
+ *   mbedtls_ssl_reset_checksum        (ssl_tls.c:838)      TLSREC_TRANSCRIPT_RESET
+ *   update_checksum                   (ssl_tls.c:896-915)  a segment's bytes
+ *   mbedtls_ssl_get_handshake_transcript (:5877-5925)      TLSREC_TRANSCRIPT_SNAPSHOT
+ *   mbedtls_ssl_reset_transcript_for_hrr
+ *                        (ssl_tls13_generic.c:1399-1441)   TLSREC_TRANSCRIPT_HRR
+ *
+ * Divergence: the reference keeps a SHA-256 and a SHA-384 operation side by
+ * side until the suite is known (ssl_update_checksum_start, ssl_tls.c:869).
+ * Here a state holds one hash and a call serves one hash; a client that has
+ * to keep both keeps two state arrays and calls twice over the same segments. */
+#define TLSREC_TRANSCRIPT_RESET     1u  /* before absorbing: the hash's initial state */
+#define TLSREC_TRANSCRIPT_SNAPSHOT  2u  /* after absorbing: digest of everything hashed so far -> out_arena + out_off;
+                                           the running state goes on (clone + finish) */
+#define TLSREC_TRANSCRIPT_HRR       4u  /* last: the state becomes that of a fresh hash over
+                                           FE 00 00 Hash.length || digest-so-far (message_hash, RFC 8446 4.4.1) */
+
+/* One connection's running hash, device-resident: plain data in a fixed layout
+ * (208 bytes, 8-byte aligned), so a state is cloned, saved or wiped with a
+ * device memcpy / memset.  All-zero is "never reset": hash is no valid id. */
+typedef struct tlsrec_transcript_state {
+    uint64_t h[8];        /* chaining words; SHA-256 uses the low halves, the high halves are zero */
+    uint64_t count;       /* bytes hashed so far; count % block size (64 / 128) is the fill level of block[] */
+    uint32_t hash;        /* TLSREC_ALG_SHA_256 or TLSREC_ALG_SHA_384; anything else: needs a RESET */
+    uint32_t reserved;    /* written as zero */
+    uint8_t  block[128];  /* the partial block as message bytes; bytes at and past the fill level are zero
+                             (SHA-256: all of block[64..128) ) */
+} tlsrec_transcript_state;
+
+typedef struct tlsrec_transcript_seg {    /* 24 bytes */
+    uint64_t off;        /* bytes to absorb: arena[off .. off + len), any alignment, len may be 0 */
+    uint64_t out_off;    /* SNAPSHOT: 48-byte element at out_arena + out_off, any alignment */
+    uint32_t len;
+    uint32_t flags;      /* TLSREC_TRANSCRIPT_* */
+} tlsrec_transcript_seg;
+
+typedef struct tlsrec_transcript_conn {   /* 16 bytes; the idiom of tlsrec_dtls_in / tlsrec_dgram */
+    uint32_t state;      /* index into states */
+    uint32_t first_seg;  /* segs[first_seg .. first_seg + nseg), applied in order */
+    uint32_t nseg;
+    uint32_t reserved;   /* zero */
+} tlsrec_transcript_conn;
+
+/* Advance nconns running hashes, one connection per lane.  hash_alg is
+ * TLSREC_ALG_SHA_256 or TLSREC_ALG_SHA_384 (the ids of the tlsrec_tls13_*
+ * calls) and holds for the whole call.  Per segment, in this order: RESET,
+ * absorb len bytes, SNAPSHOT, HRR.  The bytes are hashed as they lie: the
+ * 4-byte handshake headers of the wire (12-byte for DTLS) are part of what the
+ * caller points at, as in update_checksum(ssl->in_msg, ssl->in_hslen).
+ *
+ * A snapshot element is 48 bytes -- Hash.length digest bytes, then zeros -- the
+ * convention of tlsrec_tls13_secret, so out_off may aim at the transcript field
+ * of a tlsrec_tls13_hs_conn, at binder_transcript / hello_transcript of a
+ * tlsrec_tls13_psk_conn (a truncated ClientHello is two segments), at an
+ * element of a `transcripts` array or at tlsrec_tls12_pms_conn.session_hash.
+ *
+ * status[i] is 0 or TLSREC_ERR_SSL_BAD_INPUT_DATA: state >= nstates;
+ * first_seg + nseg past nsegs; reserved != 0; unknown flag bits; off + len
+ * past arena_len; a SNAPSHOT with out_off + 48 past out_len; a first segment
+ * without RESET on a state whose `hash` is not hash_alg (a zeroed state is
+ * one).  Every segment of a connection is validated before its first byte is
+ * absorbed: on an error the connection's state and every byte of out_arena
+ * stay as they were, and its neighbours are unaffected.  A status the kernel
+ * did not reach reads TLSREC_ERR_SSL_INTERNAL_ERROR (a prefill runs first on
+ * the same stream).  Two conns of one call that name the same state, or
+ * snapshots that overlap, are a caller error with an unspecified winner.
+ *
+ * All arrays are device memory; arena is only read, and no byte outside
+ * [arena, arena + arena_len) is read; nothing is written but the named
+ * states, the 48-byte snapshot elements and status.  Asynchronous on
+ * `stream`, no host round trip.  The lanes of a wave run as long as the
+ * longest of their 64 connections: a caller with very uneven message sizes
+ * groups connections by size.
+ *
+ * Call-level errors, in this order, before the device is touched:
+ * BAD_INPUT_DATA for another hash; for states, conns or status NULL with
+ * nconns != 0; for segs NULL with nsegs != 0; for arena NULL with
+ * arena_len != 0; for out_arena NULL with out_len != 0.  Then nconns == 0
+ * returns 0 without a launch, and HW_ACCEL_FAILED follows without a gfx950
+ * device. */
+int tlsrec_transcript_batch_update(int hash_alg, tlsrec_transcript_state *states, uint32_t nstates,
+                                   const tlsrec_transcript_conn *conns, uint32_t nconns,
+                                   const tlsrec_transcript_seg *segs, uint32_t nsegs,
+                                   const uint8_t *arena, uint64_t arena_len, uint8_t *out_arena, uint64_t out_len,
+                                   int32_t *status /* nconns */, void *stream);
+
 /* ---- engine ------------------------------------------------------------- */
 /* 0 if a gfx950 device is usable, else TLSREC_ERR_SSL_HW_ACCEL_FAILED. */
 int tlsrec_device_check(void);

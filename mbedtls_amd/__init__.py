@@ -20,6 +20,8 @@ from ._abi import (CIPHER_AES_128_GCM, CIPHER_AES_256_GCM, CIPHER_CHACHA20_POLY1
                    DTLS_OUT_BUFFER_LEN, DTLS_DROPPED, DTLS_NOT_REACHED, DTLS_ANTI_REPLAY,
                    DTLS_IGNORE_UNEXPECTED_CID, ERR_SSL_DECODE_ERROR, ERR_SSL_HELLO_VERIFY_REQUIRED,
                    COOKIE_TIMEOUT, COOKIE_LEN, DTLS_HVR_LEN, COOKIE_ITEM, CLIHLO, CLIHLO_RES,
+                   TRANSCRIPT_RESET, TRANSCRIPT_SNAPSHOT, TRANSCRIPT_HRR, TRANSCRIPT_STATE, TRANSCRIPT_SEG,
+                   TRANSCRIPT_CONN, ALG_SHA_256, ALG_SHA_384,
                    BATCH_REC, BATCH_RES, KEY_MATERIAL, load)
 from .batch import (KeyTable, batch_decrypt, batch_encrypt, frame_check, host_batch, key_material,  # noqa: F401
                     records, results, seq_bytes)
@@ -29,6 +31,7 @@ from . import cbc  # noqa: F401
 from . import tls12  # noqa: F401
 from . import cookie  # noqa: F401
 from .cookie import CookieContext  # noqa: F401
+from . import transcript  # noqa: F401
 from .tls12 import (tls_prf, tls12_compute_master, tls12_split_key_block, tls12_make_keys,  # noqa: F401
                     tls12_export_keying_material, tls12_keytab_derive, tls12_slots)
 

@@ -103,6 +103,13 @@ CLIHLO = np.dtype([("off", "<u8"), ("id_off", "<u8"), ("out_off", "<u8"), ("len"
                    ("out_cap", "<u4"), ("reserved", "<u4")])
 CLIHLO_RES = np.dtype([("status", "<i4"), ("olen", "<u4")])
 assert COOKIE_ITEM.itemsize == 24 and CLIHLO.itemsize == 40 and CLIHLO_RES.itemsize == 8
+# running handshake hashes (tlsrec_transcript_batch_update; mbedtls_amd/transcript.py)
+TRANSCRIPT_RESET, TRANSCRIPT_SNAPSHOT, TRANSCRIPT_HRR = 1, 2, 4
+TRANSCRIPT_STATE = np.dtype([("h", "<u8", 8), ("count", "<u8"), ("hash", "<u4"), ("reserved", "<u4"),
+                             ("block", "u1", 128)])
+TRANSCRIPT_SEG = np.dtype([("off", "<u8"), ("out_off", "<u8"), ("len", "<u4"), ("flags", "<u4")])
+TRANSCRIPT_CONN = np.dtype([("state", "<u4"), ("first_seg", "<u4"), ("nseg", "<u4"), ("reserved", "<u4")])
+assert TRANSCRIPT_STATE.itemsize == 208 and TRANSCRIPT_SEG.itemsize == 24 and TRANSCRIPT_CONN.itemsize == 16
 STREAM_READ_REQ = np.dtype([("out_off", "<u8"), ("out_cap", "<u4"), ("reserved", "<u4")])
 STREAM_READ_RES = np.dtype([("copied", "<u4"), ("records", "<u4"), ("left", "<u4"), ("reserved", "<u4")])
 assert STREAM_READ_REQ.itemsize == 16 and STREAM_READ_RES.itemsize == 16
@@ -338,6 +345,8 @@ SIGNATURES = {
     "tlsrec_cookie_write": (_INT, [_VP, ctypes.POINTER(_VP), _VP, _VP, _SZ]),
     "tlsrec_cookie_check": (_INT, [_VP, _VP, _SZ, _VP, _SZ]),
     "tlsrec_dtls_check_clihlo_cookies": (_INT, [_VP, ctypes.c_uint64, _VP, _U32, _VP, _VP, _VP, _VP, _VP]),
+    "tlsrec_transcript_batch_update": (_INT, [_INT, _VP, _U32, _VP, _U32, _VP, _U32, _VP, ctypes.c_uint64, _VP,
+                                              ctypes.c_uint64, _VP, _VP]),
     "tlsrec_stream_decrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_stream_read": (_INT, [_VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_stream_out_size": (ctypes.c_uint64, [_INT, _INT, _U32, ctypes.c_uint64, _U32]),

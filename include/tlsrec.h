@@ -610,6 +610,36 @@ int tlsrec_tls13_batch_ticket_psk(int hash_alg, uint32_t nonce_len, const tlsrec
                                   const uint8_t *nonces /* count x 32 bytes */, tlsrec_tls13_secret *psk,
                                   uint32_t count, void *stream);
 
+/* Batch, exporter (RFC 8446 7.5): mbedtls_ssl_tls13_exporter (ssl_tls13_keys.c:1828-1858),
+ * what mbedtls_ssl_export_keying_material (ssl_tls.c:8969) runs for a TLS 1.3 session, for
+ * each of `count` connections in one kernel:
+ *   S1 = HKDF-Expand-Label(secrets[i], label, Hash(""), Hash.length)
+ *   out[i * out_stride .. + out_len) = HKDF-Expand-Label(S1, "exporter", Hash(context i), out_len)
+ * secrets is any array of tlsrec_tls13_secret: the `exporter` of
+ * tlsrec_tls13_keytab_derive_application ("exp master"), or the `early_exporter` of
+ * tlsrec_tls13_keytab_derive_early ("e exp master"), on the same stream with nothing in
+ * between.  `label` is host memory, as in tlsrec_tls13_batch_derive_secret, and holds for the
+ * whole call; secrets, contexts and out are device memory.  Connection i's context is
+ * context_len bytes at contexts + i * context_stride; context_stride == 0 gives every
+ * connection the one context at `contexts`; contexts == NULL with context_len == 0 is no
+ * context (an empty context hashes to the same value).  Bytes [out_len, out_stride) of a row
+ * are not touched; out may not overlap an input.  Asynchronous on `stream`, no host round
+ * trip; the device inputs must stay valid until the stream reaches the call.
+ * The one divergence: a context longer than 255 bytes is TLSREC_ERR_SSL_FEATURE_UNAVAILABLE
+ * here and stays with tlsrec_tls13_exporter.
+ * Errors, in this order: TLSREC_ERR_SSL_BAD_INPUT_DATA for a hash other than SHA-256 /
+ * SHA-384; for secrets or out NULL, or contexts NULL with context_len != 0, when
+ * count != 0; for label NULL with label_len != 0; for label_len > 249 (ssl_tls.c:8959); for
+ * out_len > 8160 (MBEDTLS_SSL_EXPORT_MAX_KEY_LEN); for out_stride < out_len; for
+ * context_stride != 0 && context_stride < context_len;
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE for context_len > 255.  count == 0 or out_len == 0 then
+ * returns 0 and launches nothing; without a device TLSREC_ERR_SSL_HW_ACCEL_FAILED. */
+int tlsrec_tls13_batch_exporter(int hash_alg, const tlsrec_tls13_secret *secrets,
+                                const unsigned char *label, size_t label_len,
+                                const uint8_t *contexts, uint32_t context_len, uint32_t context_stride,
+                                uint8_t *out, uint32_t out_len, uint32_t out_stride,
+                                uint32_t count, void *stream);
+
 /* ---- TLS 1.2 / DTLS 1.2 key derivation (library/ssl_tls.c) ---------------
  * The TLS 1.2 PRF (RFC 5246 section 5, P_SHA256 / P_SHA384) on the GPU: the
  * reference's single-shot functions, and a batch that expands many
@@ -751,6 +781,38 @@ int tlsrec_tls12_batch_verify_data(int prf, int from, const tlsrec_tls12_conn *c
                                    const uint8_t *offered /* count x 16 bytes, 12 used */,
                                    uint8_t *verify /* count x 16 bytes */,
                                    uint32_t *match, uint32_t count, void *stream);
+
+/* Batch, exporter (RFC 5705): mbedtls_ssl_tls12_export_keying_material (ssl_tls.c:8886-8936),
+ * what mbedtls_ssl_export_keying_material (:8969) runs for a TLS 1.2 / DTLS 1.2 session, for
+ * each of `count` connections in one kernel:
+ *   out[i * out_stride .. + out_len) = PRF(conns[i].master, label,
+ *       client_random || server_random [|| uint16(context_len) || context i])[0..out_len)
+ * conns is the `out` of tlsrec_tls12_batch_compute_master on the same stream: randbytes is
+ * server_random || client_random, and the kernel un-swaps it as :8920-8925 does.  `label` is
+ * host memory and holds for the whole call (e.g. "EXTRACTOR-dtls_srtp", RFC 5764); conns,
+ * contexts and out are device memory.  use_context == 0 is no context: the seed ends with the
+ * randoms, and contexts, context_len and context_stride are not looked at.  With use_context
+ * connection i's context is context_len bytes at contexts + i * context_stride
+ * (context_stride == 0: the one context at `contexts` for all), and with context_len == 0 the
+ * two bytes 00 00 are still appended (:8926-8929).  Bytes [out_len, out_stride) of a row are
+ * not touched; out may not overlap an input.  Asynchronous on `stream`, no host round trip.
+ * The one divergence: a context longer than 255 bytes is TLSREC_ERR_SSL_FEATURE_UNAVAILABLE
+ * here and stays with tlsrec_tls12_export_keying_material.
+ * Errors, in the order of tlsrec_tls13_batch_exporter, so that one label array serves a
+ * terminator of both versions: TLSREC_ERR_SSL_BAD_INPUT_DATA for TLSREC_TLS_PRF_NONE or an
+ * unknown prf; for conns or out NULL, or contexts NULL with use_context and
+ * context_len != 0, when count != 0; for label NULL with label_len != 0; for
+ * label_len > 249; for out_len > 8160; for out_stride < out_len; with use_context for
+ * context_stride != 0 && context_stride < context_len;
+ * TLSREC_ERR_SSL_FEATURE_UNAVAILABLE with use_context for context_len > 255.  count == 0 or
+ * out_len == 0 then returns 0 and launches nothing; without a device
+ * TLSREC_ERR_SSL_HW_ACCEL_FAILED. */
+int tlsrec_tls12_batch_export_keying_material(int prf, const tlsrec_tls12_conn *conns,
+                                              const char *label, size_t label_len,
+                                              const uint8_t *contexts, uint32_t context_len, uint32_t context_stride,
+                                              int use_context,
+                                              uint8_t *out, uint32_t out_len, uint32_t out_stride,
+                                              uint32_t count, void *stream);
 
 /* Host-only, no GPU: the premaster of the PSK key exchanges (RFC 4279 section 2, what
  * PSA's PSK_TO_MS builds at ssl_tls.c:6307-6366),

@@ -325,6 +325,9 @@ SIGNATURES = {
     "tlsrec_tls13_batch_psk_binder": (_INT, [_INT, _U32, _INT, _VP, _VP, _VP, _VP, _U32, _VP]),
     "tlsrec_tls13_keytab_derive_early": (_INT, [_VP, _U32, _U32, _INT, _U32, _INT, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_tls13_batch_ticket_psk": (_INT, [_INT, _U32, _VP, _VP, _VP, _U32, _VP]),
+    "tlsrec_tls13_batch_exporter": (_INT, [_INT, _VP, _VP, _SZ, _VP, _U32, _U32, _VP, _U32, _U32, _U32, _VP]),
+    "tlsrec_tls12_batch_export_keying_material": (_INT, [_INT, _VP, _VP, _SZ, _VP, _U32, _U32, _INT, _VP, _U32, _U32,
+                                                         _U32, _VP]),
     "tlsrec_tls_prf": (_INT, [_INT, _VP, _SZ, ctypes.c_char_p, _VP, _SZ, _VP, _SZ]),
     "tlsrec_tls12_compute_master": (_INT, [_INT, _VP, _SZ, _VP, _SZ, _INT, _VP]),
     "tlsrec_tls12_split_key_block": (_INT, [_INT, _VP, _SZ, _VP]),
@@ -397,6 +400,17 @@ def load():
         f.argtypes = args
     _lib = L
     return L
+
+
+def tls13_exporter_blocks(hash_alg: int, label: bytes):
+    """tlsrec__tls13_exporter_blocks (host only, no GPU): the padded inner message of the
+    exporter's first Expand-Label as the batch kernel receives it.  Returns (status, words,
+    nblk): 16 * nblk big-endian words, 32-bit under SHA-256 and 64-bit under SHA-384."""
+    f = load().tlsrec__tls13_exporter_blocks
+    f.restype, f.argtypes = _INT, [_INT, _VP, _SZ, _VP, _VP]
+    words, nblk = (ctypes.c_uint64 * 80)(), _U32(0)
+    r = f(hash_alg, bytes(label) if label is not None else None, len(label or b""), words, ctypes.byref(nblk))
+    return r, list(words[:16 * nblk.value]), nblk.value
 
 
 TEST_LIB_PATH = os.path.join(PKG, "libtlsrec_test.so")

@@ -189,6 +189,18 @@ def batch_derive_secret(hash_alg: int, label: bytes, secrets, transcripts, out, 
         hash_alg, _b(label), len(label), _ptr(secrets), _ptr(transcripts), _ptr(out), count, _stream(stream)))
 
 
+def batch_exporter(hash_alg: int, secrets, label: bytes, contexts, context_len: int, context_stride: int, out,
+                   out_len: int, out_stride: int, count: int, stream=None) -> None:
+    """mbedtls_ssl_tls13_exporter (:1828) for count connections: out[i * out_stride .. + out_len)
+    from secrets[i] (count x 48 bytes on the device: the `exporter` of keytab_derive_application
+    or the `early_exporter` of keytab_derive_early).  `label`: host bytes, at most 249.
+    `contexts`: device bytes, context_len (at most 255) at i * context_stride, stride 0 = one
+    shared context, None with context_len 0 = no context."""
+    _chk("tlsrec_tls13_batch_exporter", _abi.load().tlsrec_tls13_batch_exporter(
+        hash_alg, _ptr(secrets), _b(label), len(label), _ptr(contexts), context_len, context_stride, _ptr(out),
+        out_len, out_stride, count, _stream(stream)))
+
+
 # ---- a resumed handshake in batches ------------------------------------------------
 #    ssl_tls13_offered_psks_check_binder_match (ssl_tls13_server.c:404)  -> batch_psk_binder
 #    ssl_tls13_generate_early_key (:1086) + compute_early_transform (:1184) -> keytab_derive_early

@@ -13,6 +13,7 @@ reference functions; the PRF (RFC 5246 section 5) runs in HIP kernels.
     ssl_calc_finished_tls_generic             (:7209)  -> tls12_calc_finished
     batch: the same + the check of parse_finished (:7530) -> tls12_batch_verify_data
     the RFC 4279 premaster of the PSK exchanges (:6307) -> tls12_psk_premaster (host only)
+    batch: mbedtls_ssl_tls12_export_keying_material (:8886) -> batch_export_keying_material
 
 `prf` is explicit (TLS 1.2 fixes the hash per suite, not per cipher); errors
 raise KeyScheduleError with the reference's code.
@@ -37,7 +38,8 @@ __all__ = ["PRF_NONE", "PRF_SHA384", "PRF_SHA256", "IS_CLIENT", "IS_SERVER", "CO
            "KeyScheduleError",
            "tls_prf", "tls12_compute_master", "tls12_split_key_block", "tls12_make_keys",
            "tls12_export_keying_material", "tls12_keytab_derive", "tls12_keytab_derive_cbc", "tls12_slots",
-           "tls12_batch_compute_master", "tls12_batch_verify_data", "tls12_calc_finished", "tls12_psk_premaster"]
+           "tls12_batch_compute_master", "tls12_batch_verify_data", "tls12_calc_finished", "tls12_psk_premaster",
+           "batch_export_keying_material"]
 
 
 def _key_set(ks):
@@ -147,6 +149,18 @@ def tls12_batch_verify_data(prf: int, from_: int, conns, transcripts, offered, v
     offered and match are both given or both None; verify may be None only with match."""
     _chk("tlsrec_tls12_batch_verify_data", _abi.load().tlsrec_tls12_batch_verify_data(
         prf, from_, _ptr(conns), _ptr(transcripts), _ptr(offered), _ptr(verify), _ptr(match), count, _stream(stream)))
+
+
+def batch_export_keying_material(prf: int, conns, label: bytes, contexts, context_len: int, context_stride: int,
+                                 use_context: bool, out, out_len: int, out_stride: int, count: int,
+                                 stream=None) -> None:
+    """mbedtls_ssl_tls12_export_keying_material (:8886) for count connections: out[i * out_stride
+    .. + out_len) from conns[i] (count x 112 bytes, the `out` of tls12_batch_compute_master).
+    `label`: host bytes, at most 249.  use_context False = no context; else `contexts` holds
+    context_len (at most 255) device bytes at i * context_stride, stride 0 = one shared context."""
+    _chk("tlsrec_tls12_batch_export_keying_material", _abi.load().tlsrec_tls12_batch_export_keying_material(
+        prf, _ptr(conns), _b(label), len(label), _ptr(contexts), context_len, context_stride, int(bool(use_context)),
+        _ptr(out), out_len, out_stride, count, _stream(stream)))
 
 
 def tls12_psk_premaster(psk: bytes, other: bytes | None = None, out_size: int | None = None) -> bytes:

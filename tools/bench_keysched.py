@@ -46,6 +46,15 @@ connections (tlsrec_tls12_compute_master + tlsrec_tls12_calc_finished per
 connection), and (e) the tlsrec_tls12_keytab_derive AES-128-GCM derive kernel
 under the same hash for the ns-per-compression yardstick.
 
+--exporter: the exporter batches (tlsrec_tls13_batch_exporter,
+tlsrec_tls12_batch_export_keying_material) over 64 K connections under one hash
+at three shapes -- DTLS-SRTP ("EXTRACTOR-dtls_srtp", no context, 60 bytes),
+EAP-TLS ("EXPORTER_EAP_TLS_Key_Material", a shared 1-byte context, 128 bytes),
+channel binding ("EXPORTER-Channel-Binding", no context, 32 bytes): each call,
+the single-shot call it replaces on at most 2 048 connections, and the
+tlsrec_tls12_keytab_derive AES-128-GCM derive kernel under the same hash for the
+ns-per-compression yardstick (exporters).  One JSON line per (version, shape).
+
 Prints one JSON line; the whole call and the derive kernel alone are timed
 with HIP events on the call's stream, the key-setup kernel is the difference.
 
@@ -55,6 +64,7 @@ with HIP events on the call's stream, the key-setup kernel is the difference.
     python tools/bench_keysched.py --tls13-handshake [--cipher 1|2] [--psk-len 32] [--shared-len 32]
     python tools/bench_keysched.py --tls13-early [--cipher 1|2|3] [--psk-len 32] [--no-keys]
     python tools/bench_keysched.py --tls12-handshake [--prf sha256|sha384] [--pms-len 32] [--ems]
+    python tools/bench_keysched.py --exporter [--prf sha256|sha384]
 """
 import argparse
 import ctypes
@@ -690,8 +700,127 @@ def main_tls12_handshake(a):
                                     "tls12 master secret")}))
 
 
+EXPORTER_SHAPES = {
+    # name: (label, shared context or None, bytes)
+    "dtls_srtp": (b"EXTRACTOR-dtls_srtp", None, 60),                    # RFC 5764 4.2
+    "eap_tls": (b"EXPORTER_EAP_TLS_Key_Material", b"\x0d", 128),        # RFC 9190 2.3: the one-byte type code
+    "channel_binding": (b"EXPORTER-Channel-Binding", None, 32),         # RFC 9266
+}
+
+
+def exporter_compressions(version, hname, label_len, ctx_len, out_len):
+    """SHA-2 compressions per connection of the exporter kernels (exporters); ctx_len None = no context"""
+    H, bb, lenb = (48, 128, 16) if hname == "sha384" else (32, 64, 8)
+
+    def b(nbytes):
+        return (nbytes + 1 + lenb + bb - 1) // bb
+
+    iters = (out_len + H - 1) // H
+    if version == "tls13":
+        return 2 + b(11 + label_len + H) + 1 + 2 + (b(ctx_len) if ctx_len else 0) + 2 + 3 * (iters - 1)
+    n = label_len + 64 + (0 if ctx_len is None else 2 + ctx_len)
+    return 2 + b(n) + 1 + iters * (b(H + n) + 1) + 2 * (iters - 1)
+
+
+def main_exporter(a):
+    """both exporter batches at the three deployment shapes, the host path each replaces (the single-shot call per
+    connection on at most 2 048 connections) and the key-expansion derive kernel of the same run under the same hash
+    as the ns-per-compression yardstick; one JSON line per (version, shape)"""
+    from tools import rowlib
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import keysched as K
+    from mbedtls_amd import tls12 as T
+    from mbedtls_amd.batch import _ptr, _stream
+    from tests.prng import prng_array
+    dev = torch.device("cuda")
+    L = M.load()
+    vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+    L.tlsrec__tls12_stage_keys.restype = ci
+    L.tlsrec__tls12_stage_keys.argtypes = [vp, u32, u32, ci, ci, vp, vp]
+    hname, n = a.prf, a.count
+    sha384 = hname == "sha384"
+    H = 48 if sha384 else 32
+    prf, alg = (T.PRF_SHA384, K.ALG_SHA_384) if sha384 else (T.PRF_SHA256, K.ALG_SHA_256)
+    craw = prng_array(0x715A, n * 112)
+    sraw = prng_array(0x715B, n * 48)
+    conns = torch.from_numpy(craw).to(dev)
+    secrets = torch.from_numpy(sraw).to(dev)
+    kty = M.KeyTable(2 * n)
+    s = _stream(None)
+
+    def yard():
+        r = L.tlsrec__tls12_stage_keys(kty.handle, 0, n, M.CIPHER_AES_128_GCM, prf, _ptr(conns), s)
+        assert r == 0, r
+
+    yard()
+    torch.cuda.synchronize()
+    yard_ms, _ = rowlib.event_timed(yard, a.steps)
+    yard_comp = 7 if sha384 else 13
+    yard_ns = yard_ms * 1e6 / n / yard_comp
+    nh = min(2048, n)
+    cb, sb = craw.tobytes(), sraw.tobytes()
+    for version in ("tls13", "tls12"):
+        for shape, (label, ctx, out_len) in EXPORTER_SHAPES.items():
+            stride = (out_len + 15) & ~15
+            out = torch.zeros(n * stride, dtype=torch.uint8, device=dev)
+            ctxs = None if ctx is None else torch.from_numpy(np.frombuffer(ctx, dtype=np.uint8).copy()).to(dev)
+            cl = len(ctx) if ctx else 0
+            if version == "tls13":
+                name = "tlsrec_tls13_batch_exporter"
+
+                def fn():
+                    K.batch_exporter(alg, secrets, label, ctxs, cl, 0, out, out_len, stride, n)
+
+                def one(i):
+                    return K.exporter(alg, sb[48 * i:48 * i + H], label, ctx or b"", out_len)
+            else:
+                name = "tlsrec_tls12_batch_export_keying_material"
+
+                def fn():
+                    T.batch_export_keying_material(prf, conns, label, ctxs, cl, 0, ctx is not None, out, out_len, stride, n)
+
+                def one(i):
+                    c = cb[112 * i:112 * i + 112]
+                    return T.tls12_export_keying_material(prf, c[:48], c[48:], label, ctx, out_len)
+            fn()
+            torch.cuda.synchronize()
+            ms, wall = rowlib.event_timed(fn, a.steps)
+            got = out.cpu().numpy().tobytes()
+            host = None
+            if not a.no_cpu:
+                assert one(0) == got[:out_len]
+                t0 = time.perf_counter()
+                for i in range(nh):
+                    one(i)
+                dt = time.perf_counter() - t0
+                assert one(nh - 1) == got[stride * (nh - 1):stride * (nh - 1) + out_len]
+                host = {"value": round(nh / dt), "unit": "connections/s", "kind": "single-shot", "leg": "host_path",
+                        "seconds": round(dt, 4), "sample": f"{nh} connections: the single-shot call each; wall time"}
+            comp = exporter_compressions(version, hname, len(label), None if ctx is None else len(ctx), out_len)
+            ns = ms * 1e6 / n / comp
+            cps = n / (ms / 1e3)
+            print(json.dumps({
+                "metric": "keying material exported per second", "value": round(cps), "unit": "connections/s",
+                "count": n, "version": version, "hash": hname, "shape": shape, "call": name,
+                "label_len": len(label), "context_len": None if ctx is None else len(ctx), "out_len": out_len,
+                "out_stride": stride, "ms_per_batch_events": round(ms, 4), "ms_per_batch_wall": round(wall * 1e3, 4),
+                "compressions_per_connection": comp, "ns_per_compression": round(ns, 4),
+                "per_compression_vs_stage_keys_same_run": round(ns / yard_ns, 3),
+                "stage_keys_same_run": {"cipher": M.CIPHER_AES_128_GCM, "derive_kernel_ms": round(yard_ms, 4),
+                                        "compressions_per_connection": yard_comp,
+                                        "derive_kernel_ns_per_compression": round(yard_ns, 4)},
+                "host_path": host, "speedup_vs_host_path": round(cps / host["value"], 1) if host else None,
+                "roofline": rowlib.roofline(((48 if version == "tls13" else 112) + out_len) * n, ms,
+                                            "per connection: the secret (48 bytes) or the tlsrec_tls12_conn (112) read, "
+                                            "out_len bytes written", "exporter")}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--exporter", action="store_true",
+                    help="the exporter batches (tlsrec_tls13_batch_exporter, tlsrec_tls12_batch_export_keying_material) "
+                         "at the DTLS-SRTP, EAP-TLS and channel-binding shapes under --prf")
     ap.add_argument("--tls12-handshake", action="store_true",
                     help="the TLS 1.2 handshake batches (tlsrec_tls12_batch_compute_master, _batch_verify_data)")
     ap.add_argument("--pms-len", type=int, default=32, help="--tls12-handshake: 1..128")
@@ -717,6 +846,9 @@ def main():
                     help="--tls12: an AES-CBC + HMAC suite (1 SHA-1, 2 SHA-256, 3 SHA-384), tlsrec_tls12_keytab_derive_cbc")
     ap.add_argument("--etm", action="store_true", help="--cbc-mac: encrypt-then-MAC slots")
     a = ap.parse_args()
+    if a.exporter:
+        a.prf = a.prf or "sha256"
+        return main_exporter(a)
     if a.tls12_handshake:
         a.prf = a.prf or "sha256"
         return main_tls12_handshake(a)

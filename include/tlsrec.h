@@ -1411,6 +1411,53 @@ int tlsrec_transcript_batch_update(int hash_alg, tlsrec_transcript_state *states
                                    const uint8_t *arena, uint64_t arena_len, uint8_t *out_arena, uint64_t out_len,
                                    int32_t *status /* nconns */, void *stream);
 
+/* ---- X25519 key exchange in batches (x25519.hip) ------------------------
+ * The (EC)DHE step in front of the key schedule, for the group x25519 (RFC 7748): what the
+ * reference does through psa_generate_key + psa_export_public_key (ssl_tls13_generic.c:
+ * 1566-1582) and psa_raw_key_agreement (ssl_tls13_keys.c:1457; ssl_tls12_server.c:2603-2631,
+ * :3028).  One connection per lane.  Every array is a device array; both calls are
+ * asynchronous on `stream` with no host round trip, and the inputs must stay valid until the
+ * stream reaches the call.
+ *
+ * priv is count x 32 bytes, packed: 32 random bytes per connection, which the kernel clamps
+ * (decodeScalar25519, RFC 7748 section 5).  The reference destroys the private key after the
+ * agreement (psa_destroy_key, ssl_tls13_keys.c:1467); priv is only read here, so the caller
+ * wipes it once the stream has passed the call (a hipMemsetAsync on the same stream does).
+ * Generating the 32 bytes is the caller's.
+ *
+ * Each stride is at least 32.  Exactly 32 bytes per element are written, as the canonical
+ * little-endian encoding; bytes between the elements are not touched.  Loads and stores are
+ * 16-byte ones where the pointer and the stride are 16-byte aligned, byte ones otherwise.
+ *
+ * Errors of both calls, in this order, before the GPU is touched:
+ * TLSREC_ERR_SSL_BAD_INPUT_DATA for a NULL array with count != 0, then for a stride below
+ * 32.  count == 0 then returns 0 and launches nothing; without a gfx950 device
+ * TLSREC_ERR_SSL_HW_ACCEL_FAILED.  There is no single-shot host-pointer form. */
+
+/* pub[pub_stride * i .. + 32) = X25519(priv[32 i ..], 9)   (RFC 7748 section 5, section 6.1) */
+int tlsrec_x25519_batch_public(const uint8_t *priv, uint8_t *pub, uint32_t pub_stride,
+                               uint32_t count, void *stream);
+
+/* out[out_stride * i .. + 32) = X25519(priv[32 i ..], peer[peer_stride * i ..]);
+ * ok[i] = 1 unless those 32 bytes are all zero, then 0 (RFC 8446 section 7.4.2, RFC 7748
+ * section 6.1).  Bit 255 of the peer's u-coordinate is masked; the non-canonical values
+ * 2^255 - 19 .. 2^255 - 1 are accepted and reduced, as the RFC requires.  out_stride lets
+ * the call write where the next one reads:
+ *   out = (uint8_t *) conns + offsetof(tlsrec_tls13_hs_conn, shared), stride 176, for
+ *         tlsrec_tls13_keytab_derive_handshake with shared_len 32;
+ *   out = (uint8_t *) pms_conns, stride 240, for tlsrec_tls12_batch_compute_master with
+ *         pms_len 32 (the TLS 1.2 ECDHE premaster is the raw 32 bytes);
+ *   packed, stride 32.
+ * ok is one uint32_t per connection (the convention of `match` in
+ * tlsrec_tls12_batch_verify_data), computed from the OR of the eight output words with no
+ * branch on the data.  It must not be NULL when count != 0: the RFCs' check is a MUST, so
+ * the call does not let the caller skip it.  A connection with ok[i] == 0 has an all-zero
+ * output: the caller drops it, and whatever the later stages derive for that connection
+ * must not be trusted. */
+int tlsrec_x25519_batch_shared(const uint8_t *priv, const uint8_t *peer, uint32_t peer_stride,
+                               uint8_t *out, uint32_t out_stride, uint32_t *ok,
+                               uint32_t count, void *stream);
+
 /* ---- engine ------------------------------------------------------------- */
 /* 0 if a gfx950 device is usable, else TLSREC_ERR_SSL_HW_ACCEL_FAILED. */
 int tlsrec_device_check(void);

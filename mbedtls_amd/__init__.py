@@ -32,6 +32,7 @@ from . import tls12  # noqa: F401
 from . import cookie  # noqa: F401
 from .cookie import CookieContext  # noqa: F401
 from . import transcript  # noqa: F401
+from . import x25519  # noqa: F401
 from .tls12 import (tls_prf, tls12_compute_master, tls12_split_key_block, tls12_make_keys,  # noqa: F401
                     tls12_export_keying_material, tls12_keytab_derive, tls12_slots)
 

@@ -350,6 +350,8 @@ SIGNATURES = {
     "tlsrec_dtls_check_clihlo_cookies": (_INT, [_VP, ctypes.c_uint64, _VP, _U32, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_transcript_batch_update": (_INT, [_INT, _VP, _U32, _VP, _U32, _VP, _U32, _VP, ctypes.c_uint64, _VP,
                                               ctypes.c_uint64, _VP, _VP]),
+    "tlsrec_x25519_batch_public": (_INT, [_VP, _VP, _U32, _U32, _VP]),
+    "tlsrec_x25519_batch_shared": (_INT, [_VP, _VP, _U32, _VP, _U32, _VP, _U32, _VP]),
     "tlsrec_stream_decrypt": (_INT, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP]),
     "tlsrec_stream_read": (_INT, [_VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tlsrec_stream_out_size": (ctypes.c_uint64, [_INT, _INT, _U32, ctypes.c_uint64, _U32]),
@@ -411,6 +413,17 @@ def tls13_exporter_blocks(hash_alg: int, label: bytes):
     words, nblk = (ctypes.c_uint64 * 80)(), _U32(0)
     r = f(hash_alg, bytes(label) if label is not None else None, len(label or b""), words, ctypes.byref(nblk))
     return r, list(words[:16 * nblk.value]), nblk.value
+
+
+def x25519_host(scalar: bytes, point: bytes):
+    """tlsrec__x25519_host (host only, no GPU; for the CPU tests, not a fallback): the ladder of
+    csrc/tlsrec_x25519.h on the CPU.  Returns (32 output bytes, ok)."""
+    f = load().tlsrec__x25519_host
+    f.restype, f.argtypes = _INT, [_VP, ctypes.c_char_p, ctypes.c_char_p]
+    assert len(scalar) == 32 and len(point) == 32
+    out = ctypes.create_string_buffer(32)
+    ok = f(out, bytes(scalar), bytes(point))
+    return out.raw, ok
 
 
 TEST_LIB_PATH = os.path.join(PKG, "libtlsrec_test.so")

@@ -55,6 +55,14 @@ the single-shot call it replaces on at most 2 048 connections, and the
 tlsrec_tls12_keytab_derive AES-128-GCM derive kernel under the same hash for the
 ns-per-compression yardstick (exporters).  One JSON line per (version, shape).
 
+--x25519: the key exchange in front of all of the above (tlsrec_x25519_batch_public,
+tlsrec_x25519_batch_shared): (a) and (b) the two calls alone at 4 096, 65 536 and 1 048 576
+connections, (c) the chain batch_shared -> tlsrec_tls13_keytab_derive_handshake
+(AES-128-GCM, no PSK) as one enqueue at --count connections, with the share of it that is
+the key exchange, and (d) the CPU path it replaces: OpenSSL EVP_PKEY_derive, one worker
+process per CPU of the share (at most 16), with one context, timing the derive alone
+(through ctypes).  One JSON line per leg.
+
 Prints one JSON line; the whole call and the derive kernel alone are timed
 with HIP events on the call's stream, the key-setup kernel is the difference.
 
@@ -65,6 +73,7 @@ with HIP events on the call's stream, the key-setup kernel is the difference.
     python tools/bench_keysched.py --tls13-early [--cipher 1|2|3] [--psk-len 32] [--no-keys]
     python tools/bench_keysched.py --tls12-handshake [--prf sha256|sha384] [--pms-len 32] [--ems]
     python tools/bench_keysched.py --exporter [--prf sha256|sha384]
+    python tools/bench_keysched.py --x25519 [--count 65536]
 """
 import argparse
 import ctypes
@@ -816,8 +825,117 @@ def main_exporter(a):
                                             "out_len bytes written", "exporter")}), flush=True)
 
 
+# ---- X25519 -----------------------------------------------------------------------------------
+def x25519_cpu_worker(seconds):
+    """one process of the CPU leg: EVP_PKEY_derive over fresh key pairs for `seconds`; prints its count"""
+    from tests import x25519_ref as R
+    from tests.prng import prng_bytes
+    if R.lib() is None:
+        print(0)
+        return
+    L = R.lib()
+    raw = prng_bytes(os.getpid(), 64)
+    # one context for the process, set up outside the timed loop (making the private key object costs a
+    # ladder of its own, which the reference pays in psa_generate_key, not in the agreement)
+    key = L.EVP_PKEY_new_raw_private_key(R.EVP_PKEY_X25519, None, raw[:32], 32)
+    peer = L.EVP_PKEY_new_raw_public_key(R.EVP_PKEY_X25519, None, R.model(raw[32:], R.BASE), 32)
+    ctx = L.EVP_PKEY_CTX_new(key, None)
+    assert L.EVP_PKEY_derive_init(ctx) == 1 and L.EVP_PKEY_derive_set_peer(ctx, peer) == 1
+    out, ln = ctypes.create_string_buffer(32), ctypes.c_size_t(32)
+    n, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(64):
+            assert L.EVP_PKEY_derive(ctx, out, ctypes.byref(ln)) == 1
+        n += 64
+    print(n / (time.perf_counter() - t0))
+
+
+def x25519_cpu_leg(seconds):
+    """EVP_PKEY_derive per second on min(16, CPUs) worker processes, none of which opens the GPU"""
+    import subprocess
+    workers = max(1, min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS", "16"))))
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--x25519-cpu-worker", "--cpu-seconds",
+                               str(seconds)], stdout=subprocess.PIPE, text=True) for _ in range(workers)]
+    rates = [float(p.communicate()[0].strip() or 0) for p in procs]
+    return {"kind": "evp", "workers": workers, "derives_per_second": round(sum(rates)),
+            "per_worker": round(sum(rates) / workers), "seconds": seconds,
+            "note": "EVP_PKEY_derive alone, one context per worker process, through ctypes"}
+
+
+def main_x25519(a):
+    cpu = None if a.no_cpu else x25519_cpu_leg(a.cpu_seconds)      # before this process opens the GPU
+    import torch
+    import mbedtls_amd as M
+    from mbedtls_amd import keysched as K, x25519 as XK
+    from tests.prng import prng_array
+    dev = torch.device("cuda")
+    st = torch.cuda.current_stream()
+    rep = "ten signed limbs of 25.5 bits, 64-bit products"
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+        for s, e in ev:
+            s.record(st)
+            fn()
+            e.record(st)
+        torch.cuda.synchronize()
+        return [s.elapsed_time(e) for s, e in ev]
+
+    def row(leg, count, ms, **extra):
+        m = float(np.median(ms))
+        r = {"metric": "X25519 per second", "leg": leg, "count": count, "value": round(count / (m / 1e3)),
+             "unit": "connections/s", "ms_per_call_median": round(m, 4), "ms_per_call": [round(x, 4) for x in ms],
+             "representation": rep}
+        if cpu and cpu["derives_per_second"]:
+            r["ratio_to_cpu"] = round(r["value"] / cpu["derives_per_second"], 2)
+        r.update(extra)
+        print(json.dumps(r), flush=True)
+        return m
+
+    if cpu:
+        print(json.dumps({"metric": "X25519 per second", "leg": "cpu_evp_pkey_derive", **cpu}), flush=True)
+    for count in (4096, 65536, 1048576):
+        priv = torch.from_numpy(prng_array(0x255 + count, count * 32)).to(dev)
+        pub = torch.zeros(count * 32, dtype=torch.uint8, device=dev)
+        out = torch.zeros(count * 32, dtype=torch.uint8, device=dev)
+        ok = torch.zeros(count, dtype=torch.int32, device=dev)
+        row("batch_public", count, timed(lambda: XK.batch_public(priv, pub, count)))
+        row("batch_shared", count, timed(lambda: XK.batch_shared(priv, pub, out, ok, count)))
+        assert int(ok.sum()) == count
+    # the chain: the shared secret lands in hs_conn.shared, the handshake stage follows on the stream
+    count, cipher = a.count, M.CIPHER_AES_128_GCM
+    priv = torch.from_numpy(prng_array(0x2551, count * 32)).to(dev)
+    pub = torch.zeros(count * 32, dtype=torch.uint8, device=dev)
+    XK.batch_public(priv, pub, count)
+    conns = torch.from_numpy(prng_array(0x2552, count * K.HS_CONN_BYTES)).to(dev)
+    ok = torch.zeros(count, dtype=torch.int32, device=dev)
+    hs, ms_ = (torch.zeros(n * 48, dtype=torch.uint8, device=dev) for n in (2 * count, count))
+    kt = M.KeyTable(2 * count)
+    dst, stride = XK.into_hs_conns(conns)
+
+    def stage():
+        K.keytab_derive_handshake(kt, 0, count, cipher, 0, 32, conns, hs, None, ms_)
+
+    def chain():
+        XK.batch_shared(priv, pub, dst, ok, count, out_stride=stride)
+        stage()
+
+    t_stage = float(np.median(timed(stage)))
+    t_x = float(np.median(timed(lambda: XK.batch_shared(priv, pub, dst, ok, count, out_stride=stride))))
+    row("chain batch_shared -> tls13_keytab_derive_handshake", count, timed(chain),
+        ms_handshake_stage_alone=round(t_stage, 4), ms_batch_shared_alone=round(t_x, 4),
+        key_exchange_share_of_chain=round(t_x / (t_x + t_stage), 4))
+    kt.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--x25519", action="store_true",
+                    help="the key exchange batches (tlsrec_x25519_batch_public, _batch_shared) and their chain into "
+                         "the TLS 1.3 handshake stage")
+    ap.add_argument("--x25519-cpu-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--exporter", action="store_true",
                     help="the exporter batches (tlsrec_tls13_batch_exporter, tlsrec_tls12_batch_export_keying_material) "
                          "at the DTLS-SRTP, EAP-TLS and channel-binding shapes under --prf")
@@ -846,6 +964,10 @@ def main():
                     help="--tls12: an AES-CBC + HMAC suite (1 SHA-1, 2 SHA-256, 3 SHA-384), tlsrec_tls12_keytab_derive_cbc")
     ap.add_argument("--etm", action="store_true", help="--cbc-mac: encrypt-then-MAC slots")
     a = ap.parse_args()
+    if a.x25519_cpu_worker:
+        return x25519_cpu_worker(a.cpu_seconds)
+    if a.x25519:
+        return main_x25519(a)
     if a.exporter:
         a.prf = a.prf or "sha256"
         return main_exporter(a)

@@ -339,7 +339,7 @@ extern "C" uint32_t tlsrec_cbc_minlen(int mac, int etm)
     return (etm ? ml + 16 : ml + 16 - ml % 16) + 16;
 }
 
-/* Device-side producers of key material (keysched.hip) write into the
+/* Device-side producers of key material (keysched.hip, tls13_ladder.hip, tls12_batch.hip) write into the
  * table's staging area and then commit: bookkeeping as tlsrec_keytab_load,
  * then the key-setup kernel on the staged slots. */
 extern "C" tlsrec_key_material *tlsrec__keytab_stage(tlsrec_keytab *kt) { return kt->d_stage; }

@@ -232,6 +232,13 @@ int tlsrec__batch_sized(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, t
                         int prefilled, int cbc);
 /* the table holds (or has held) a CBC slot */
 int tlsrec__keytab_has_cbc(const tlsrec_keytab *kt);
+/* engine.hip: the table's device staging areas, which the key-derivation kernels write key material into, and the
+ * bookkeeping + key setup of `count` slots from `first` staged there */
+tlsrec_key_material *tlsrec__keytab_stage(tlsrec_keytab *kt);
+int tlsrec__keytab_commit_staged(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, hipStream_t st);
+tlsrec_cbc_key_material *tlsrec__keytab_stage_cbc(tlsrec_keytab *kt);
+int tlsrec__keytab_commit_staged_cbc(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, int mac, int etm,
+                                     hipStream_t st);
 /* encrypt with each record's content read from in_arena + src_off[i] (GcmArgs::
  * src_off) and the records written to out_arena at buf_off: the stream / DTLS
  * send path without a copy of the application data.  Only for key tables of
@@ -289,6 +296,15 @@ enum {
     TLSREC_LOG_CBC = 9,
     TLSREC_LOG_CBC_KERNEL = 10
 };
+/* not exported from the library: shared between its units only */
+#define TLSREC_LOCAL __attribute__((visibility("hidden")))
+
+/* keysched.hip: the single-shot calls' device arena (32 KiB) and its stream, for a unit that stages a batch of one
+ * there (cookie.hip).  tlsrec_ks_arena_lock creates both on first use; on 0 the caller holds the arena's lock until
+ * tlsrec_ks_arena_unlock, on an error it holds nothing. */
+TLSREC_LOCAL int tlsrec_ks_arena_lock(uint8_t **dev, hipStream_t *stream);
+TLSREC_LOCAL void tlsrec_ks_arena_unlock(void);
+
 #ifdef TLSREC_TEST_HOOKS
 extern "C" void tlsrec__test_launch_log_add(int32_t kind, int32_t p0, int32_t p1, int32_t p2, int32_t p3);
 #define TLSREC_LAUNCH_LOG(kind, p0, p1, p2, p3) \

@@ -1,6 +1,7 @@
 /*
  * tlsrec_sha.h -- the word-wise SHA-2 compression the one-lane-per-connection
- * kernels share (keysched.hip: the TLS 1.2 / 1.3 ladders and the cookies;
+ * kernels share (tlsrec_kdf.h and its units: the TLS 1.2 / 1.3 ladders, the
+ * exporters and the cookies;
  * transcript.hip: the running handshake hashes): round constants, the
  * per-hash traits S256 / S512 with their initial values, one round, one block.
  *

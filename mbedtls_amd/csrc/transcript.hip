@@ -10,7 +10,7 @@
  *                        ssl_tls13_generic.c:1399-1441       TLSREC_TRANSCRIPT_HRR
  *
  * One connection per lane, 64 lanes per workgroup, no LDS, on sha_compress<T>
- * of tlsrec_sha.h like the ladders of keysched.hip.  A lane loads its state
+ * of tlsrec_sha.h like the ladders of tls13_ladder.hip.  A lane loads its state
  * (chaining words, byte count, partial block), walks its segments and stores
  * the state back.  The message window is 16 words in registers, addressed in
  * 32-bit big-endian cells (16 to a SHA-256 block, 32 to a SHA-512 one).

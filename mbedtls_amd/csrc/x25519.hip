@@ -9,7 +9,7 @@
  *                          ssl_tls12_server.c:2603-2631, :3028   x25519_kernel<false>
  *
  * One connection per lane, 64 lanes per workgroup, no LDS, like the ladders of
- * keysched.hip.  The arithmetic is tlsrec_x25519.h, the same body the host
+ * tls13_ladder.hip.  The arithmetic is tlsrec_x25519.h, the same body the host
  * export tlsrec__x25519_host runs for the CPU tests.  A lane loads its scalar
  * (and the peer's u-coordinate) as eight words, runs the ladder and stores 32
  * bytes: 16-byte accesses where pointer and stride are 16-byte aligned, bytes

@@ -1,4 +1,4 @@
-"""GPU parity of the DTLS cookie batch (keysched.hip through the C ABI):
+"""GPU parity of the DTLS cookie batch (cookie.hip through the C ABI):
 tlsrec_cookie_batch_write / _check, tlsrec_dtls_check_clihlo_cookies and the
 single-shot callbacks against the checker of tests/cookie_ref.py (hmac /
 hashlib), every status and every output byte bit-exact -- over the id lengths

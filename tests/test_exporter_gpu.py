@@ -1,4 +1,4 @@
-"""GPU parity of the exporter batches (keysched.hip, through the C ABI):
+"""GPU parity of the exporter batches (exporter.hip, through the C ABI):
 tlsrec_tls13_batch_exporter and tlsrec_tls12_batch_export_keying_material against
 the hashlib models of tests/exporter_ref.py (and, for TLS 1.3,
 the oracle) -- every output byte bit-exact, and every byte around the rows

@@ -1,4 +1,4 @@
-"""GPU parity of the TLS 1.2 / DTLS 1.2 handshake batches (keysched.hip, through
+"""GPU parity of the TLS 1.2 / DTLS 1.2 handshake batches (tls12_batch.hip, through
 the C ABI): tlsrec_tls12_batch_compute_master and tlsrec_tls12_batch_verify_data
 against the checker of tests/tls12_hs_ref.py (P_hash over hashlib, cross-checked
 by OpenSSL's TLS1-PRF) -- every output byte bit-exact over the premaster lengths

@@ -1,4 +1,4 @@
-"""GPU parity of the TLS 1.2 / DTLS 1.2 key derivation (keysched.hip, through
+"""GPU parity of the TLS 1.2 / DTLS 1.2 key derivation (tls12_batch.hip, through
 the C ABI): the reference's own PRF vectors (tests/golden/tls12_prf.json), the
 single-shot calls against two independent checkers (P_hash over hashlib and
 OpenSSL's EVP_KDF "TLS1-PRF", tests/tls12_ref.py) on the sizes where the block,

@@ -1,4 +1,4 @@
-"""GPU parity of the resumed-handshake batches (keysched.hip, through the C ABI):
+"""GPU parity of the resumed-handshake batches (tls13_ladder.hip, through the C ABI):
 tlsrec_tls13_batch_psk_binder, tlsrec_tls13_keytab_derive_early and
 tlsrec_tls13_batch_ticket_psk against the reference's RFC 8448 vectors and the
 hashlib checker of tests/tls13_early_ref.py -- every output array bit-exact at

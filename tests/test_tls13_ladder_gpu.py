@@ -1,4 +1,4 @@
-"""GPU parity of the TLS 1.3 ladder (keysched.hip, through the C ABI): the
+"""GPU parity of the TLS 1.3 ladder (tls13_ladder.hip, through the C ABI): the
 single-shot helpers, Finished MAC and PSK binder against the reference's own
 vectors (tests/golden/tls13_handshake.json) and the hashlib ladder of
 tests/tls13_ref.py, and the batch stages -- every output array bit-exact at the

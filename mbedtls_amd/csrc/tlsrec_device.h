@@ -516,6 +516,33 @@ __device__ __forceinline__ void gmul_word_or(const uint8_t *lds, uint32_t base, 
     }
 }
 
+/* gmul_word_or<PI, 2> in two halves (wave phasing, below): the reads, the XORs */
+template <int PI>
+__device__ __forceinline__ void gmul_half_issue(const uint8_t *lds, uint32_t base, uint32_t wd, int d, int e0,
+                                                uint4 (&v)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int e = e0 + i;
+        const int b = 4 * d + e;
+        const uint32_t ahi = base | ((e == 0) ? (wd & 0xf0u) : ((wd >> (8 * e)) & 0xf0u));
+        const uint32_t alo = base | ((e == 0) ? ((wd << 4) & 0xf0u) : ((wd >> (8 * e - 4)) & 0xf0u));
+        v[2 * i] = *reinterpret_cast<const uint4 *>(lds + ahi + PI * 8192 + (2 * b) * 256);
+        v[2 * i + 1] = *reinterpret_cast<const uint4 *>(lds + alo + PI * 8192 + (2 * b + 1) * 256);
+    }
+}
+
+__device__ __forceinline__ void gmul_half_tail(const uint4 (&v)[4], uint4 &acc)
+{
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        acc.x = xor3(acc.x, v[2 * i].x, v[2 * i + 1].x);
+        acc.y = xor3(acc.y, v[2 * i].y, v[2 * i + 1].y);
+        acc.z = xor3(acc.z, v[2 * i].z, v[2 * i + 1].z);
+        acc.w = xor3(acc.w, v[2 * i].w, v[2 * i + 1].w);
+    }
+}
+
 /* ---------------- GHASH with 5-bit position tables (G5) ------------------ *
  * ds_read_b64 serves 32 lanes per LDS cycle over all 64 banks, so a 256-byte
  * image of 32 eight-byte entries is conflict-free for any index: a 5-bit
@@ -637,6 +664,86 @@ __device__ __forceinline__ void aes_round(const uint8_t *lds, uint32_t lb, RK rk
     s0 = t0; s1 = t1; s2 = t2; s3 = t3;
 }
 
+/* Wave phasing of the 16-wave key passes (aes_ghash<..., PHASE = true>): a
+ * round is split into its issue half -- the 16 T-table addresses and reads,
+ * and the GHASH phase's -- at priority PRIO_ISSUE, and its tail (XOR / rotate,
+ * GHASH accumulation; after the last round the payload XOR and the store) at
+ * PRIO_TAIL, so that a wave whose reads have returned queues its next reads
+ * ahead of sibling waves doing work the LDS does not wait for.  s_setprio
+ * also keeps the compiler from moving reads across it.  Same box, A B B A,
+ * 3 repetitions (r07, profiles/r07/ab/c2_variants.jsonl): c2 761.7-769.9 ->
+ * 787.3-798.2 GiB/s (medians 766.4 -> 792.8, +3.4 %) at 3 / 0; a start offset
+ * of the waves (s_sleep by wave) on top of it measured no further gain and
+ * alone none. */
+constexpr int PRIO_ISSUE = 3;
+constexpr int PRIO_TAIL = 0;
+
+template <int AES_OFF>
+__device__ __forceinline__ void aes_round_issue(const uint8_t *lds, uint32_t lb, uint32_t s0, uint32_t s1,
+                                                uint32_t s2, uint32_t s3, uint32_t (&v)[16])
+{
+    const uint32_t s[4] = { s0, s1, s2, s3 };
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        v[4 * c + 0] = tlook<AES_OFF>(lds, s[c], lb, 0, 0);
+        v[4 * c + 1] = tlook<AES_OFF>(lds, s[(c + 1) & 3], lb, 1, 1);
+        v[4 * c + 2] = tlook<AES_OFF>(lds, s[(c + 2) & 3], lb, 2, 0);
+        v[4 * c + 3] = tlook<AES_OFF>(lds, s[(c + 3) & 3], lb, 3, 1);
+    }
+}
+
+template <typename RK>
+__device__ __forceinline__ void aes_round_tail(RK rk, int r, const uint32_t (&v)[16], uint32_t &s0, uint32_t &s1,
+                                               uint32_t &s2, uint32_t &s3)
+{
+    s0 = xor3(v[0], v[1], rotl16(xor3(v[2], v[3], rk[4 * r + 0])));
+    s1 = xor3(v[4], v[5], rotl16(xor3(v[6], v[7], rk[4 * r + 1])));
+    s2 = xor3(v[8], v[9], rotl16(xor3(v[10], v[11], rk[4 * r + 2])));
+    s3 = xor3(v[12], v[13], rotl16(xor3(v[14], v[15], rk[4 * r + 3])));
+}
+
+/* phase G of a G5 multiply (gmul5_phase) in two halves: the reads, the XORs */
+template <int K, int K1>
+__device__ __forceinline__ void gmul5_issue_k(const uint8_t *lds, const uint32_t (&w)[4], uint2 (&v)[8])
+{
+    if constexpr (K < K1) {
+        const uint32_t a = g5_addr<K>(w);
+        constexpr int i = 2 * (K1 - 1 - K);           /* any fixed slot per window */
+        v[i] = *reinterpret_cast<const uint2 *>(lds + a + K * 256);
+        v[i + 1] = *reinterpret_cast<const uint2 *>(lds + g5_hi(a) + G5_HI + K * 256);
+        gmul5_issue_k<K + 1, K1>(lds, w, v);
+    }
+}
+
+template <int G>
+__device__ __forceinline__ void gmul5_phase_issue(const uint8_t *lds, const uint32_t (&w)[4], uint2 (&v)[8])
+{
+    constexpr int K0 = G < 2 ? 4 * G : 8 + 3 * (G - 2);
+    constexpr int NK = G < 2 ? 4 : 3;
+    gmul5_issue_k<K0, K0 + NK>(lds, w, v);
+}
+
+template <int G>
+__device__ __forceinline__ void gmul5_phase_tail(const uint2 (&v)[8], uint4 &acc)
+{
+    constexpr int NK = G < 2 ? 4 : 3;
+    acc.x = xor3(acc.x, v[0].x, v[2].x);
+    acc.y = xor3(acc.y, v[0].y, v[2].y);
+    acc.z = xor3(acc.z, v[1].x, v[3].x);
+    acc.w = xor3(acc.w, v[1].y, v[3].y);
+    if constexpr (NK == 4) {
+        acc.x = xor3(acc.x, v[4].x, v[6].x);
+        acc.y = xor3(acc.y, v[4].y, v[6].y);
+        acc.z = xor3(acc.z, v[5].x, v[7].x);
+        acc.w = xor3(acc.w, v[5].y, v[7].y);
+    } else {
+        acc.x ^= v[4].x;
+        acc.y ^= v[4].y;
+        acc.z ^= v[5].x;
+        acc.w ^= v[5].y;
+    }
+}
+
 /* ---------------- counter-mode round caching -------------------------- *
  * Within one record the GCM counter block is (N0, N1, N2, BE32(ctr)) with
  * ctr < 2^16, so after whitening only rows 2 and 3 of column 3 vary: round 1
@@ -671,6 +778,27 @@ __device__ __forceinline__ CtrCache ctr_cache(const uint8_t *lds, uint32_t lb, R
 #undef TB
 }
 
+/* Phase boundary of aes_ghash after GHASH group g: an empty asm re-defines the
+ * AES state, the accumulator and the source words still to be read (G5
+ * phases read windows across word boundaries, so a word stays one group
+ * longer), so no read moves into an earlier phase. */
+template <bool G5>
+__device__ __forceinline__ void ghash_phase_fence(int g, uint32_t &s0, uint32_t &s1, uint32_t &s2, uint32_t &s3,
+                                                  uint4 &acc, uint32_t (&w)[4])
+{
+    asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3), "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w));
+    if constexpr (G5) {
+        if (g < 2) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+        else if (g < 4) asm volatile("" : "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+        else if (g < 6) asm volatile("" : "+v"(w[2]), "+v"(w[3]));
+        else asm volatile("" : "+v"(w[3]));
+    } else {
+        if (g < 2) asm volatile("" : "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+        else if (g < 4) asm volatile("" : "+v"(w[2]), "+v"(w[3]));
+        else if (g < 6) asm volatile("" : "+v"(w[3]));
+    }
+}
+
 /* Fused counter-block encryption and one GHASH multiply, for a step whose
  * GHASH input does not depend on this step's keystream:
  *     ks = E_K(N0, N1, N2, ctrw),  prod = y * P_PI
@@ -681,14 +809,16 @@ __device__ __forceinline__ CtrCache ctr_cache(const uint8_t *lds, uint32_t lb, R
  * asm statements are the phase boundaries: they re-define the AES state, the
  * accumulator and the source words still to be read, so no read moves into an
  * earlier phase (bounded reads in flight and VGPRs, no memory clobber). */
-template <int NR, int AES_OFF, int PI, int R0 = 2, int RS = 1, bool G5 = false, typename RK>
+template <int NR, int AES_OFF, int PI, int R0 = 2, int RS = 1, bool G5 = false, bool PHASE = false, typename RK>
 __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh, uint32_t lb, RK rk,
                                           const CtrCache &cc, uint32_t ctrw, uint4 y, uint4 &ks, uint4 &prod)
 {
     static_assert(R0 >= 2 && R0 + 7 * RS <= NR - 1, "GHASH groups must fall on middle rounds 2..NR-1");
+    static_assert(!PHASE || (R0 == 2 && RS == 1), "PHASE: one GHASH phase per round from round 2");
 #define TA(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 0)
 #define TB(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 1)
     uint32_t s0, s1, s2, s3;
+    if constexpr (PHASE) __builtin_amdgcn_s_setprio(PRIO_ISSUE);
     {
         const uint32_t w3 = ctrw ^ rk[3];
         const uint32_t t0 = rotl16(cc.k0r ^ TB(w3, 3));
@@ -704,12 +834,50 @@ __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh,
     uint4 acc = make_uint4(0, 0, 0, 0);
 #pragma unroll
     for (int r = 2; r < NR; r++) {
-        if (r > 2) aes_round<AES_OFF>(lds, lb, rk, r, s0, s1, s2, s3);
         const int g = (r - R0) / RS;
+        if constexpr (PHASE) {
+            /* issue half at PRIO_ISSUE, tail at PRIO_TAIL (above) */
+            uint32_t tv[16];
+            uint2 g5v[8];
+            uint4 g4v[4];
+            if (r > 2) {
+                __builtin_amdgcn_s_setprio(PRIO_ISSUE);
+                aes_round_issue<AES_OFF>(lds, lb, s0, s1, s2, s3, tv);
+            }
+            if (g < 8) {
+                if constexpr (G5) {
+                    switch (g) {
+                        case 0: gmul5_phase_issue<0>(gh, w, g5v); break;
+                        case 1: gmul5_phase_issue<1>(gh, w, g5v); break;
+                        case 2: gmul5_phase_issue<2>(gh, w, g5v); break;
+                        case 3: gmul5_phase_issue<3>(gh, w, g5v); break;
+                        case 4: gmul5_phase_issue<4>(gh, w, g5v); break;
+                        case 5: gmul5_phase_issue<5>(gh, w, g5v); break;
+                        case 6: gmul5_phase_issue<6>(gh, w, g5v); break;
+                        default: gmul5_phase_issue<7>(gh, w, g5v); break;
+                    }
+                } else {
+                    /* TLSREC_GH_OR = 0: the table through its pointer, as gmul_word does */
+                    gmul_half_issue<PI>(TLSREC_GH_OR ? lds : gh, TLSREC_GH_OR ? (uint32_t) (gh - lds) : 0u, w[g >> 1],
+                                        g >> 1, 2 * (g & 1), g4v);
+                }
+            }
+            __builtin_amdgcn_s_setprio(PRIO_TAIL);
+            if (r > 2) aes_round_tail(rk, r, tv, s0, s1, s2, s3);
+            if (g < 8) {
+                if constexpr (G5) {
+                    if (g < 2) gmul5_phase_tail<0>(g5v, acc);
+                    else gmul5_phase_tail<2>(g5v, acc);
+                } else {
+                    gmul_half_tail(g4v, acc);
+                }
+                ghash_phase_fence<G5>(g, s0, s1, s2, s3, acc, w);
+            }
+            continue;
+        }
+        if (r > 2) aes_round<AES_OFF>(lds, lb, rk, r, s0, s1, s2, s3);
         if (r >= R0 && (r - R0) % RS == 0 && g < 8) {
             if constexpr (G5) {
-                /* G5 phases read windows across word boundaries: every word
-                 * still read enters the next phase through the barrier */
                 switch (g) {
                     case 0: gmul5_phase<0>(gh, w, acc); break;
                     case 1: gmul5_phase<1>(gh, w, acc); break;
@@ -720,28 +888,38 @@ __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh,
                     case 6: gmul5_phase<6>(gh, w, acc); break;
                     default: gmul5_phase<7>(gh, w, acc); break;
                 }
-                asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3), "+v"(acc.x), "+v"(acc.y), "+v"(acc.z),
-                             "+v"(acc.w));
-                if (g < 2) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
-                else if (g < 4) asm volatile("" : "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
-                else if (g < 6) asm volatile("" : "+v"(w[2]), "+v"(w[3]));
-                else asm volatile("" : "+v"(w[3]));
             } else {
                 if constexpr (TLSREC_GH_OR)
                     gmul_word_or<PI, 2>(lds, (uint32_t) (gh - lds), w[g >> 1], g >> 1, acc, 2 * (g & 1));
                 else
                     gmul_word<PI, 2>(gh, w[g >> 1], g >> 1, acc, 2 * (g & 1));
-                asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3), "+v"(acc.x), "+v"(acc.y), "+v"(acc.z),
-                             "+v"(acc.w));
-                /* the words still to be read enter the next phase through the barrier */
-                if (g < 2) asm volatile("" : "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
-                else if (g < 4) asm volatile("" : "+v"(w[2]), "+v"(w[3]));
-                else if (g < 6) asm volatile("" : "+v"(w[3]));
             }
+            ghash_phase_fence<G5>(g, s0, s1, s2, s3, acc, w);
         }
     }
     uint32_t o[4];
     const uint32_t s[4] = { s0, s1, s2, s3 };
+    if constexpr (PHASE) {
+        uint32_t fv[16];
+        __builtin_amdgcn_s_setprio(PRIO_ISSUE);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            fv[4 * c + 0] = tlook<AES_OFF>(lds, s[c], lb, 0, 0);
+            fv[4 * c + 1] = tlook<AES_OFF>(lds, s[(c + 1) & 3], lb, 1, 0);
+            fv[4 * c + 2] = tlook<AES_OFF>(lds, s[(c + 2) & 3], lb, 2, 0);
+            fv[4 * c + 3] = tlook<AES_OFF>(lds, s[(c + 3) & 3], lb, 3, 0);
+        }
+        __builtin_amdgcn_s_setprio(PRIO_TAIL);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            uint32_t lo = __builtin_amdgcn_perm(fv[4 * c + 1], fv[4 * c + 0], 0x0C0C0501u);
+            uint32_t hi = __builtin_amdgcn_perm(fv[4 * c + 3], fv[4 * c + 2], 0x06020C0Cu);
+            o[c] = __builtin_amdgcn_bitop3_b32(lo, hi, rk[4 * NR + c], 0x56);
+        }
+        ks = make_uint4(o[0], o[1], o[2], o[3]);
+        prod = acc;
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         uint32_t a = tlook<AES_OFF>(lds, s[c], lb, 0, 0);

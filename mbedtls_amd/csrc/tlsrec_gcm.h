@@ -235,6 +235,7 @@ __global__ __launch_bounds__(W * 64) void tlsrec_gcm_kernel(GcmArgs a)
     constexpr int NTHR = W * 64;
     constexpr int LOGL = Log2<L>::v;
     constexpr int R = 64 / L;
+    constexpr bool KP = !WP && !PAIR && !CID && !ARIA && W == 16;   /* the 16-wave AES key passes */
     /* the kernel's only LDS object, so it starts at LDS address 0 and every
      * table offset folds into the ds_read immediate */
     __shared__ __attribute__((aligned(16))) uint8_t lds[LY::BYTES];
@@ -576,7 +577,8 @@ __global__ __launch_bounds__(W * 64) void tlsrec_gcm_kernel(GcmArgs a)
                     auto crypt = [&](int32_t cc, uint4 y, uint4 &ks, uint4 &Zn) {
                         const uint32_t ctrw = bswap32((uint32_t) cc + 2u);
                         if constexpr (CACHED) {
-                            aes_ghash<NR, LY::AES, HPI, 2, 1, G5>(lds, hor, lanebase, rk, ccache, ctrw, y, ks, Zn);
+                            /* KP: wave phasing, the round's reads at a raised priority (tlsrec_device.h) */
+                            aes_ghash<NR, LY::AES, HPI, 2, 1, G5, KP>(lds, hor, lanebase, rk, ccache, ctrw, y, ks, Zn);
                         } else {
                             if constexpr (ARIA)
                                 ks = alt_encrypt<NR, LY::AES>(lds, lanebase, rk, make_uint4(jb.nw0, jb.nw1, jb.nw2, ctrw));

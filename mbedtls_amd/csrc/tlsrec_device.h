@@ -95,28 +95,15 @@ typedef const __attribute__((address_space(4))) uint32_t kconst_u32;
  * in every step. */
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) u32x4 glob_u32x4;
-/* TLSREC_NT_DATA (A/B builds): bit 0 loads, bit 1 stores of record payload
- * with the non-temporal hint */
-#ifndef TLSREC_NT_DATA
-#define TLSREC_NT_DATA 0
-#endif
 __device__ __forceinline__ uint4 gload16(const uint8_t *p)
 {
-#if TLSREC_NT_DATA & 1
-    const u32x4 v = __builtin_nontemporal_load((const glob_u32x4 *) (uintptr_t) p);
-#else
     const u32x4 v = *(const glob_u32x4 *) (uintptr_t) p;
-#endif
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void gstore16(uint8_t *p, uint4 v)
 {
     u32x4 w = { v.x, v.y, v.z, v.w };
-#if TLSREC_NT_DATA & 2
-    __builtin_nontemporal_store(w, (glob_u32x4 *) (uintptr_t) p);
-#else
     *(glob_u32x4 *) (uintptr_t) p = w;
-#endif
 }
 
 #define TLSREC_PSEL(k) (0x0C0C0000u | ((4u + (k)) << 8))
@@ -471,32 +458,11 @@ __device__ __forceinline__ uint4 gmul(const uint8_t *lds, uint4 y)
     return acc;
 }
 
-/* Part of gmul: the table reads of bytes e0 .. e0+NE-1 of 32-bit word d of y. */
-template <int PI, int NE = 4>
-__device__ __forceinline__ void gmul_word(const uint8_t *lds, uint32_t wd, int d, uint4 &acc, int e0 = 0)
-{
-#pragma unroll
-    for (int i = 0; i < NE; i++) {
-        const int e = e0 + i;
-        const int b = 4 * d + e;
-        uint32_t ahi = (e == 0) ? (wd & 0xf0u) : ((wd >> (8 * e)) & 0xf0u);
-        uint32_t alo = (e == 0) ? ((wd << 4) & 0xf0u) : ((wd >> (8 * e - 4)) & 0xf0u);
-        uint4 th = *reinterpret_cast<const uint4 *>(lds + ahi + PI * 8192 + (2 * b) * 256);
-        uint4 tl = *reinterpret_cast<const uint4 *>(lds + alo + PI * 8192 + (2 * b + 1) * 256);
-        acc.x = xor3(acc.x, th.x, tl.x);
-        acc.y = xor3(acc.y, th.y, tl.y);
-        acc.z = xor3(acc.z, th.z, tl.z);
-        acc.w = xor3(acc.w, th.w, tl.w);
-    }
-}
-
-/* gmul_word with the table at LDS offset base (a multiple of 256) of the
- * kernel's LDS array lds: the entry address as base | (nibble x 16) --
- * one v_and_or per read where lds-relative pointer arithmetic took a shift,
- * a mask and an add (r06; the paired passes' tables sit at a per-pair base) */
-#ifndef TLSREC_GH_OR
-#define TLSREC_GH_OR 1
-#endif
+/* Part of gmul: the table reads of bytes e0 .. e0+NE-1 of 32-bit word d of y,
+ * with the table at LDS offset base (a multiple of 256) of the kernel's LDS
+ * array lds: the entry address as base | (nibble x 16) -- one v_and_or per
+ * read where lds-relative pointer arithmetic took a shift, a mask and an add
+ * (r06; the paired passes' tables sit at a per-pair base) */
 template <int PI, int NE = 4>
 __device__ __forceinline__ void gmul_word_or(const uint8_t *lds, uint32_t base, uint32_t wd, int d, uint4 &acc,
                                              int e0 = 0)
@@ -624,15 +590,6 @@ __device__ __forceinline__ void gmul5_part(const uint8_t *lds, const uint32_t (&
     }
 }
 
-/* phase g (0..7) of a G5 multiply: windows [3g + min(g, 2), ...): 4,4,3,3,3,3,3,3 */
-template <int G>
-__device__ __forceinline__ void gmul5_phase(const uint8_t *lds, const uint32_t (&w)[4], uint4 &acc)
-{
-    constexpr int K0 = G < 2 ? 4 * G : 8 + 3 * (G - 2);
-    constexpr int NK = G < 2 ? 4 : 3;
-    gmul5_part<K0, NK>(lds, w, acc);
-}
-
 /* y * P with P's G5 table at lds (whole multiply, four phases of 6-7 windows) */
 __device__ __forceinline__ uint4 gmul5(const uint8_t *lds, uint4 y)
 {
@@ -702,7 +659,8 @@ __device__ __forceinline__ void aes_round_tail(RK rk, int r, const uint32_t (&v)
     s3 = xor3(v[12], v[13], rotl16(xor3(v[14], v[15], rk[4 * r + 3])));
 }
 
-/* phase G of a G5 multiply (gmul5_phase) in two halves: the reads, the XORs */
+/* phase G (0..7) of a G5 multiply, windows [3G + min(G, 2), ...): 4,4,3,3,3,3,3,3,
+ * in two halves: the reads, the XORs */
 template <int K, int K1>
 __device__ __forceinline__ void gmul5_issue_k(const uint8_t *lds, const uint32_t (&w)[4], uint2 (&v)[8])
 {
@@ -778,6 +736,25 @@ __device__ __forceinline__ CtrCache ctr_cache(const uint8_t *lds, uint32_t lb, R
 #undef TB
 }
 
+/* Rounds 1-2 of the counter block (N0, N1, N2, ctrw) from the record's cache:
+ * the state after round 2, 10 lookups. */
+template <int AES_OFF, typename RK>
+__device__ __forceinline__ void ctr_cache_rounds(const uint8_t *lds, uint32_t lb, RK rk, const CtrCache &cc,
+                                                 uint32_t ctrw, uint32_t &s0, uint32_t &s1, uint32_t &s2, uint32_t &s3)
+{
+#define TA(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 0)
+#define TB(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 1)
+    const uint32_t w3 = ctrw ^ rk[3];
+    const uint32_t t0 = rotl16(cc.k0r ^ TB(w3, 3));
+    const uint32_t t1 = rotl16(cc.k1r ^ TA(w3, 2));
+    s0 = xor3(TA(t0, 0), TB(t1, 1), cc.d0);
+    s1 = xor3(TA(t1, 0), cc.d1, rotl16(TB(t0, 3)));
+    s2 = rotl16(xor3(TA(t0, 2), TB(t1, 3), cc.d2r));
+    s3 = xor3(TB(t0, 1), cc.d3, rotl16(TA(t1, 2)));
+#undef TA
+#undef TB
+}
+
 /* Phase boundary of aes_ghash after GHASH group g: an empty asm re-defines the
  * AES state, the accumulator and the source words still to be read (G5
  * phases read windows across word boundaries, so a word stays one group
@@ -803,38 +780,25 @@ __device__ __forceinline__ void ghash_phase_fence(int g, uint32_t &s0, uint32_t 
  * GHASH input does not depend on this step's keystream:
  *     ks = E_K(N0, N1, N2, ctrw),  prod = y * P_PI
  * (ctrw = BE32(ctr) as a little-endian word, ctr < 2^16, rounds 1-2 from `cc`).
- * The 32 GHASH table reads are issued in 8 groups of 4 (a half word of y),
- * group g after AES round R0 + g*RS, each sharing its phase with that
- * round's T-table reads so the LDS sees both streams at once.  The empty
- * asm statements are the phase boundaries: they re-define the AES state, the
- * accumulator and the source words still to be read, so no read moves into an
- * earlier phase (bounded reads in flight and VGPRs, no memory clobber). */
-template <int NR, int AES_OFF, int PI, int R0 = 2, int RS = 1, bool G5 = false, bool PHASE = false, typename RK>
+ * The GHASH table reads are issued in 8 groups (a half word of y: 4 reads of
+ * the 4-bit table at gh; G5: 3-4 windows), group g with AES round 2 + g, each
+ * sharing its phase with that round's T-table reads so the LDS sees both
+ * streams at once.  ghash_phase_fence ends a phase (bounded reads in flight
+ * and VGPRs, no memory clobber).  PHASE: wave phasing (above). */
+template <int NR, int AES_OFF, int PI, bool G5 = false, bool PHASE = false, typename RK>
 __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh, uint32_t lb, RK rk,
                                           const CtrCache &cc, uint32_t ctrw, uint4 y, uint4 &ks, uint4 &prod)
 {
-    static_assert(R0 >= 2 && R0 + 7 * RS <= NR - 1, "GHASH groups must fall on middle rounds 2..NR-1");
-    static_assert(!PHASE || (R0 == 2 && RS == 1), "PHASE: one GHASH phase per round from round 2");
-#define TA(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 0)
-#define TB(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 1)
+    static_assert(NR >= 10, "GHASH groups 0..7 fall on middle rounds 2..9");
+    static_assert(PHASE || !G5, "the G5 table is read by the phased key passes only");
     uint32_t s0, s1, s2, s3;
     if constexpr (PHASE) __builtin_amdgcn_s_setprio(PRIO_ISSUE);
-    {
-        const uint32_t w3 = ctrw ^ rk[3];
-        const uint32_t t0 = rotl16(cc.k0r ^ TB(w3, 3));
-        const uint32_t t1 = rotl16(cc.k1r ^ TA(w3, 2));
-        s0 = xor3(TA(t0, 0), TB(t1, 1), cc.d0);
-        s1 = xor3(TA(t1, 0), cc.d1, rotl16(TB(t0, 3)));
-        s2 = rotl16(xor3(TA(t0, 2), TB(t1, 3), cc.d2r));
-        s3 = xor3(TB(t0, 1), cc.d3, rotl16(TA(t1, 2)));
-    }
-#undef TA
-#undef TB
+    ctr_cache_rounds<AES_OFF>(lds, lb, rk, cc, ctrw, s0, s1, s2, s3);
     uint32_t w[4] = { y.x, y.y, y.z, y.w };
     uint4 acc = make_uint4(0, 0, 0, 0);
 #pragma unroll
     for (int r = 2; r < NR; r++) {
-        const int g = (r - R0) / RS;
+        const int g = r - 2;
         if constexpr (PHASE) {
             /* issue half at PRIO_ISSUE, tail at PRIO_TAIL (above) */
             uint32_t tv[16];
@@ -846,6 +810,8 @@ __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh,
             }
             if (g < 8) {
                 if constexpr (G5) {
+                    /* written out here: behind a helper, or as a compile-time
+                     * index, the G5 kernels allocate registers differently */
                     switch (g) {
                         case 0: gmul5_phase_issue<0>(gh, w, g5v); break;
                         case 1: gmul5_phase_issue<1>(gh, w, g5v); break;
@@ -857,9 +823,7 @@ __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh,
                         default: gmul5_phase_issue<7>(gh, w, g5v); break;
                     }
                 } else {
-                    /* TLSREC_GH_OR = 0: the table through its pointer, as gmul_word does */
-                    gmul_half_issue<PI>(TLSREC_GH_OR ? lds : gh, TLSREC_GH_OR ? (uint32_t) (gh - lds) : 0u, w[g >> 1],
-                                        g >> 1, 2 * (g & 1), g4v);
+                    gmul_half_issue<PI>(lds, (uint32_t) (gh - lds), w[g >> 1], g >> 1, 2 * (g & 1), g4v);
                 }
             }
             __builtin_amdgcn_s_setprio(PRIO_TAIL);
@@ -873,30 +837,17 @@ __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh,
                 }
                 ghash_phase_fence<G5>(g, s0, s1, s2, s3, acc, w);
             }
-            continue;
-        }
-        if (r > 2) aes_round<AES_OFF>(lds, lb, rk, r, s0, s1, s2, s3);
-        if (r >= R0 && (r - R0) % RS == 0 && g < 8) {
-            if constexpr (G5) {
-                switch (g) {
-                    case 0: gmul5_phase<0>(gh, w, acc); break;
-                    case 1: gmul5_phase<1>(gh, w, acc); break;
-                    case 2: gmul5_phase<2>(gh, w, acc); break;
-                    case 3: gmul5_phase<3>(gh, w, acc); break;
-                    case 4: gmul5_phase<4>(gh, w, acc); break;
-                    case 5: gmul5_phase<5>(gh, w, acc); break;
-                    case 6: gmul5_phase<6>(gh, w, acc); break;
-                    default: gmul5_phase<7>(gh, w, acc); break;
-                }
-            } else {
-                if constexpr (TLSREC_GH_OR)
-                    gmul_word_or<PI, 2>(lds, (uint32_t) (gh - lds), w[g >> 1], g >> 1, acc, 2 * (g & 1));
-                else
-                    gmul_word<PI, 2>(gh, w[g >> 1], g >> 1, acc, 2 * (g & 1));
+        } else {
+            /* the same round as expressions: on the issue / tail helpers the
+             * unphased kernels schedule differently */
+            if (r > 2) aes_round<AES_OFF>(lds, lb, rk, r, s0, s1, s2, s3);
+            if (g < 8) {
+                gmul_word_or<PI, 2>(lds, (uint32_t) (gh - lds), w[g >> 1], g >> 1, acc, 2 * (g & 1));
+                ghash_phase_fence<G5>(g, s0, s1, s2, s3, acc, w);
             }
-            ghash_phase_fence<G5>(g, s0, s1, s2, s3, acc, w);
         }
     }
+    /* last round: S[x] is byte 1 (and byte 2) of T0[x]; PHASE: all reads, then all combines */
     uint32_t o[4];
     const uint32_t s[4] = { s0, s1, s2, s3 };
     if constexpr (PHASE) {
@@ -916,88 +867,20 @@ __device__ __forceinline__ void aes_ghash(const uint8_t *lds, const uint8_t *gh,
             uint32_t hi = __builtin_amdgcn_perm(fv[4 * c + 3], fv[4 * c + 2], 0x06020C0Cu);
             o[c] = __builtin_amdgcn_bitop3_b32(lo, hi, rk[4 * NR + c], 0x56);
         }
-        ks = make_uint4(o[0], o[1], o[2], o[3]);
-        prod = acc;
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        uint32_t a = tlook<AES_OFF>(lds, s[c], lb, 0, 0);
-        uint32_t b = tlook<AES_OFF>(lds, s[(c + 1) & 3], lb, 1, 0);
-        uint32_t d2 = tlook<AES_OFF>(lds, s[(c + 2) & 3], lb, 2, 0);
-        uint32_t d3 = tlook<AES_OFF>(lds, s[(c + 3) & 3], lb, 3, 0);
-        uint32_t lo = __builtin_amdgcn_perm(b, a, 0x0C0C0501u);
-        uint32_t hi = __builtin_amdgcn_perm(d3, d2, 0x06020C0Cu);
-        o[c] = __builtin_amdgcn_bitop3_b32(lo, hi, rk[4 * NR + c], 0x56);
-    }
-    ks = make_uint4(o[0], o[1], o[2], o[3]);
-    prod = acc;
-}
-
-/* NB independent counter blocks of one record and NB independent GHASH
- * multiplies per call (NB Horner chains per lane), phase-interleaved as in
- * aes_ghash: chain b's group g of 4 table reads follows AES round 2 + g. */
-template <int NR, int AES_OFF, int PI, int NB, typename RK>
-__device__ __forceinline__ void aes_ghash_n(const uint8_t *lds, uint32_t lb, RK rk, const CtrCache &cc,
-                                            const uint32_t (&ctrw)[NB], const uint4 (&y)[NB], uint4 (&ks)[NB],
-                                            uint4 (&prod)[NB])
-{
-    static_assert(NR >= 10, "rounds 2..9 carry the GHASH groups");
-#define TA(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 0)
-#define TB(x, k) tlook<AES_OFF>(lds, (x), lb, (k), 1)
-    uint32_t s[NB][4];
-    uint32_t w[NB][4];
-    uint4 acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        const uint32_t w3 = ctrw[b] ^ rk[3];
-        const uint32_t t0 = rotl16(cc.k0r ^ TB(w3, 3));
-        const uint32_t t1 = rotl16(cc.k1r ^ TA(w3, 2));
-        s[b][0] = xor3(TA(t0, 0), TB(t1, 1), cc.d0);
-        s[b][1] = xor3(TA(t1, 0), cc.d1, rotl16(TB(t0, 3)));
-        s[b][2] = rotl16(xor3(TA(t0, 2), TB(t1, 3), cc.d2r));
-        s[b][3] = xor3(TB(t0, 1), cc.d3, rotl16(TA(t1, 2)));
-        w[b][0] = y[b].x; w[b][1] = y[b].y; w[b][2] = y[b].z; w[b][3] = y[b].w;
-        acc[b] = make_uint4(0, 0, 0, 0);
-    }
-#undef TA
-#undef TB
-#pragma unroll
-    for (int r = 2; r < NR; r++) {
-        if (r > 2) {
-#pragma unroll
-            for (int b = 0; b < NB; b++) aes_round<AES_OFF>(lds, lb, rk, r, s[b][0], s[b][1], s[b][2], s[b][3]);
-        }
-        const int g = r - 2;
-        if (g < 8) {
-#pragma unroll
-            for (int b = 0; b < NB; b++) gmul_word<PI, 2>(lds, w[b][g >> 1], g >> 1, acc[b], 2 * (g & 1));
-#pragma unroll
-            for (int b = 0; b < NB; b++) {
-                asm volatile("" : "+v"(s[b][0]), "+v"(s[b][1]), "+v"(s[b][2]), "+v"(s[b][3]), "+v"(acc[b].x),
-                             "+v"(acc[b].y), "+v"(acc[b].z), "+v"(acc[b].w));
-                if (g < 2) asm volatile("" : "+v"(w[b][1]), "+v"(w[b][2]), "+v"(w[b][3]));
-                else if (g < 4) asm volatile("" : "+v"(w[b][2]), "+v"(w[b][3]));
-                else if (g < 6) asm volatile("" : "+v"(w[b][3]));
-            }
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        uint32_t o[4];
+    } else {
 #pragma unroll
         for (int c = 0; c < 4; c++) {
-            uint32_t a = tlook<AES_OFF>(lds, s[b][c], lb, 0, 0);
-            uint32_t bb = tlook<AES_OFF>(lds, s[b][(c + 1) & 3], lb, 1, 0);
-            uint32_t d2 = tlook<AES_OFF>(lds, s[b][(c + 2) & 3], lb, 2, 0);
-            uint32_t d3 = tlook<AES_OFF>(lds, s[b][(c + 3) & 3], lb, 3, 0);
-            uint32_t lo = __builtin_amdgcn_perm(bb, a, 0x0C0C0501u);
+            uint32_t a = tlook<AES_OFF>(lds, s[c], lb, 0, 0);
+            uint32_t b = tlook<AES_OFF>(lds, s[(c + 1) & 3], lb, 1, 0);
+            uint32_t d2 = tlook<AES_OFF>(lds, s[(c + 2) & 3], lb, 2, 0);
+            uint32_t d3 = tlook<AES_OFF>(lds, s[(c + 3) & 3], lb, 3, 0);
+            uint32_t lo = __builtin_amdgcn_perm(b, a, 0x0C0C0501u);
             uint32_t hi = __builtin_amdgcn_perm(d3, d2, 0x06020C0Cu);
             o[c] = __builtin_amdgcn_bitop3_b32(lo, hi, rk[4 * NR + c], 0x56);
         }
-        ks[b] = make_uint4(o[0], o[1], o[2], o[3]);
-        prod[b] = acc[b];
     }
+    ks = make_uint4(o[0], o[1], o[2], o[3]);
+    prod = acc;
 }
 
 __device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }

@@ -4,7 +4,7 @@
 # the other objects of build/
 # (run `python -m mbedtls_amd.build` first).  Measurement only -- the product
 # library is mbedtls_amd/libtlsrec.so, built by mbedtls_amd/build.py.
-#   tools/build_variant.sh <name> <hipcc flags...>    e.g.  abl1 -DTLSREC_ABLATE=1
+#   tools/build_variant.sh <name> <hipcc flags...>    e.g.  UNITS=stream tools/build_variant.sh fk8 -DTLSREC_STREAM_FK=8
 set -euo pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

@@ -6,7 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "tlsrec_device.h"
+#include "aes_ghash_n.h"     /* tlsrec_device.h + the NB-block step */
 #include "tlsrec_bitslice.h"
 
 using namespace tlsrec;

@@ -3,7 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Imbedtls_amd/csrc tools/ilp_probe.hip -o tools_bin/ilp_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include "tlsrec_device.h"
+#include "aes_ghash_n.h"     /* tlsrec_device.h + the NB-block step */
 
 using namespace tlsrec;
 constexpr int AESOFF = 40960;   /* after 5 GHASH tables */

@@ -36,15 +36,16 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wno-unuse
 C_FLAGS = ["-O2", "-fPIC", "-std=c11", "-Wall", "-Wextra", "-I" + INC, "-I" + CSRC]
 
 HEADERS = ["tlsrec_device.h", "tlsrec_frame.h", "tlsrec_internal.h", "tlsrec_recdev.h", "tlsrec_gcm.h", "tlsrec_cbc.h",
-           "tlsrec_plan.h", "tlsrec_cbc_kernel.h", "tlsrec_cbc_wave.h", "tlsrec_altkey.h", "tlsrec_sha.h", "tlsrec_kdf.h", "tlsrec_x25519.h"]
+           "tlsrec_plan.h", "tlsrec_keytab.h", "tlsrec_cbc_kernel.h", "tlsrec_cbc_wave.h", "tlsrec_altkey.h", "tlsrec_sha.h", "tlsrec_kdf.h", "tlsrec_x25519.h"]
 UNITS = [("gcm_dec.hip", "hip"), ("gcm_enc.hip", "hip"), ("gcm_alt_dec.hip", "hip"), ("gcm_alt_enc.hip", "hip"),
-         ("kernels.hip", "hip"), ("engine.hip", "hip"), ("keysched.hip", "hip"), ("tls13_ladder.hip", "hip"), ("tls12_batch.hip", "hip"),
+         ("kernels.hip", "hip"), ("keytab.hip", "hip"), ("scratch.hip", "hip"), ("batch.hip", "hip"), ("host_pipe.hip", "hip"),
+         ("engine.hip", "hip"), ("keysched.hip", "hip"), ("tls13_ladder.hip", "hip"), ("tls12_batch.hip", "hip"),
          ("exporter.hip", "hip"), ("cookie.hip", "hip"), ("stream.hip", "hip"), ("ccm.hip", "hip"), ("cbc.hip", "hip"), ("cbc_alt.hip", "hip"), ("cbc_wave.hip", "hip"),
          ("ticket.hip", "hip"), ("transcript.hip", "hip"), ("x25519.hip", "hip"),
          ("server.hip", "hip"), ("tlsrec_host.c", "c")]
 # units whose code changes under TLSREC_TEST_HOOKS (TLSREC_HOOK_SKIP, the hook entry points)
 # (stream.hip: only its host-side dispatchers, which append to the launch log; tlsrec_host.c: the pinned CBC IV)
-HOOK_UNITS = {"gcm_dec.hip", "gcm_enc.hip", "gcm_alt_dec.hip", "gcm_alt_enc.hip", "kernels.hip", "engine.hip",
+HOOK_UNITS = {"gcm_dec.hip", "gcm_enc.hip", "gcm_alt_dec.hip", "gcm_alt_enc.hip", "kernels.hip", "batch.hip", "engine.hip",
               "ccm.hip", "cbc.hip", "cbc_alt.hip", "cbc_wave.hip", "server.hip", "stream.hip", "tlsrec_host.c"}
 
 

@@ -44,9 +44,6 @@ using tlsrec::cbc_body_len;
 using tlsrec::cbc_is_cipher;
 using tlsrec::cbc_maclen;
 
-/* engine.hip */
-extern "C" const SlotState *tlsrec__keytab_slots(const tlsrec_keytab *kt);
-
 namespace tlsst {
 
 constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;

@@ -343,11 +343,6 @@ __global__ __launch_bounds__(TK_THREADS) void tlsrec_ticket_kernel(TicketArgs a)
 
 using namespace tlsrec;
 
-/* engine.hip */
-extern "C" const SlotState *tlsrec__keytab_slots(const tlsrec_keytab *kt);
-extern "C" const uint4 *tlsrec__keytab_ghtab(const tlsrec_keytab *kt);
-extern "C" int tlsrec__keytab_cipher(const tlsrec_keytab *kt, uint32_t slot);
-
 static int ticket_batch(const tlsrec_keytab *kt, const tlsrec_ticket_keys *keys, const tlsrec_ticket *t, uint32_t n,
                         uint8_t *arena, tlsrec_ticket_res *res, void *stream, bool dec)
 {

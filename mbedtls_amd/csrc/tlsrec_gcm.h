@@ -442,7 +442,7 @@ __global__ __launch_bounds__(W * 64) void tlsrec_gcm_kernel(GcmArgs a)
                 /* the paired passes are compiled for lane powers only (r06): with
                  * the fold and the two final multiplies by H as a value in them too,
                  * their out-of-line calls cost 28 spilled VGPRs whose stores ran in
-                 * every round (engine.hip picks the 8-wave passes for the other
+                 * every round (gcm_plan picks the 8-wave passes for the other
                  * TREEMUL modes) */
                 const bool lp = PAIR || (WP && !CID && (a.tm & 8u));
                 const bool lenx = lp && m % BL == 0;

@@ -22,7 +22,7 @@
 #include "tlsrec.h"
 #include "tlsrec_frame.h"
 
-/* engine.hip */
+/* engine.hip, keytab.hip */
 int tlsrec__engine_slot_alloc(const tlsrec_key_material *km);
 void tlsrec__engine_slot_free(int slot);
 int tlsrec__engine_run(int dec, const tlsrec_batch_rec *rec, unsigned char *buf, size_t buf_len,

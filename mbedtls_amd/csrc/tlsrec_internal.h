@@ -9,7 +9,13 @@
 
 #include "tlsrec.h"
 
+/* not exported from the library: shared between its units only */
+#define TLSREC_LOCAL __attribute__((visibility("hidden")))
+
 namespace tlsrec {
+
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline int hip_ok(hipError_t e) { return e == hipSuccess ? 0 : TLSREC_ERR_SSL_HW_ACCEL_FAILED; }
 
 /* Test hooks, the reference's MBEDTLS_TEST_HOOKS (ssl_misc.h:2685): only the
  * test build (libtlsrec_test.so, -DTLSREC_TEST_HOOKS, tests/ only) can leave a
@@ -179,7 +185,40 @@ struct CbcArgs {
     uint32_t skip;            /* test hook, as GcmArgs::skip */
 };
 
+/* Launch options of one batch (batch.hip):
+ *   only_mask  launch only these ciphers' kernels (1 << TLSREC_CIPHER_*; the
+ *              single-record engine knows its records' ciphers), 0 = every
+ *              cipher the table holds
+ *   avg_bytes  mean record size when the caller knows it (the stream / DTLS
+ *              layers, the host pipeline; 0 = unknown) -- it decides the GCM
+ *              launch for many keys with little work each
+ *   prefilled  the caller already wrote INTERNAL_ERROR into every result (the
+ *              single-record engine stages it with the upload)
+ *   coalesced  a few records of many connections gathered from concurrent
+ *              single-record calls: identity order (no bucket pass: its four
+ *              launches would cost more than the batch), GCM in 16-lane wave
+ *              passes, so each wave serves its own record's key */
+struct BatchOpt {
+    uint32_t only_mask = 0;
+    uint32_t avg_bytes = 0;
+    bool prefilled = false;
+    bool coalesced = false;
+    bool grouped = false;                /* a key's records are contiguous (the stream / DTLS layers: a connection's
+                                            records in order): no bucket pass, the kernels walk them in place */
+    const uint64_t *src_off = nullptr;   /* encrypt: contents at in + src_off[i] (tlsrec__batch_src) */
+    bool no_cbc = false;                 /* the stream / DTLS layers without TLSREC_FRAME_CBC: a CBC slot counts as
+                                            never loaded (no CBC kernel; its records get the bad-slot result) */
+};
+
+/* batch.hip: what tlsrec_batch_encrypt / _decrypt run, for the units that set options of their own (the host
+ * pipeline, the single-record engine) */
+TLSREC_LOCAL int batch(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tlsrec_batch_res *res, uint32_t n,
+                       const uint8_t *in, uint8_t *out, uint32_t lanes, void *stream, int dec,
+                       const BatchOpt &opt = BatchOpt());
+
 } /* namespace tlsrec */
+
+struct HostPipe;   /* host_pipe.hip: a table's device slots and streams for tlsrec_host_batch_*, made on first use */
 
 extern "C" {
 hipError_t tlsrec__launch_cbc(const tlsrec::CbcArgs *a, int dec, uint32_t variants, hipStream_t st);
@@ -206,7 +245,7 @@ hipError_t tlsrec__launch_gcm(const tlsrec::GcmArgs *a, int dec, int lanes, int 
                               hipStream_t st);
 hipError_t tlsrec__launch_chachapoly(const tlsrec::CpArgs *a, int dec, int lanes, uint32_t grid,
                                      hipStream_t st);
-/* Per-(device, stream, kind) device scratch, reused across calls (engine.hip).
+/* Per-(device, stream, kind) device scratch, reused across calls (scratch.hip).
  * Work enqueued on one stream is ordered, so a stream's scratch can be
  * reused by its next call without waiting; the lease's lock keeps two host
  * threads from interleaving their enqueues on one stream's scratch.  (The
@@ -232,7 +271,7 @@ int tlsrec__batch_sized(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, t
                         int prefilled, int cbc);
 /* the table holds (or has held) a CBC slot */
 int tlsrec__keytab_has_cbc(const tlsrec_keytab *kt);
-/* engine.hip: the table's device staging areas, which the key-derivation kernels write key material into, and the
+/* keytab.hip: the table's device staging areas, which the key-derivation kernels write key material into, and the
  * bookkeeping + key setup of `count` slots from `first` staged there */
 tlsrec_key_material *tlsrec__keytab_stage(tlsrec_keytab *kt);
 int tlsrec__keytab_commit_staged(tlsrec_keytab *kt, uint32_t first, uint32_t count, int cipher, hipStream_t st);
@@ -248,6 +287,29 @@ int tlsrec__batch_src(const tlsrec_keytab *kt, const tlsrec_batch_rec *recs, tls
                       const uint8_t *in_arena, uint8_t *out_arena, void *stream, uint32_t avg_bytes,
                       const uint64_t *src_off);
 int tlsrec__keytab_src_ok(const tlsrec_keytab *kt);
+/* keytab.hip: the slots' expanded state and tables (device memory), and the host mirror of a slot's cipher
+ * (0 = holds no key) */
+const tlsrec::SlotState *tlsrec__keytab_slots(const tlsrec_keytab *kt);
+const uint4 *tlsrec__keytab_ghtab(const tlsrec_keytab *kt);
+int tlsrec__keytab_cipher(const tlsrec_keytab *kt, uint32_t slot);
+/* the single-record engine gives a slot back: its state, cipher byte and tables zeroized on `st`, waited for, and
+ * the slot out of the table's bookkeeping */
+TLSREC_LOCAL void tlsrec__keytab_slot_zeroize(tlsrec_keytab *kt, uint32_t slot, hipStream_t st);
+/* the table's host pipeline (NULL until host_pipe.hip makes it), under the table's lock until _unlock;
+ * tlsrec_keytab_free ends it with tlsrec__host_pipe_free */
+TLSREC_LOCAL HostPipe **tlsrec__keytab_pipe_lock(tlsrec_keytab *kt);
+TLSREC_LOCAL void tlsrec__keytab_pipe_unlock(tlsrec_keytab *kt);
+TLSREC_LOCAL void tlsrec__host_pipe_free(HostPipe *p);
+/* batch.hip: the record index the AEAD kernels leave unreached (tlsrec__test_skip_record; 0xffffffff = none,
+ * and always in the release library) */
+TLSREC_LOCAL uint32_t tlsrec__test_skip(void);
+/* server.hip, the resident record server (AES-GCM, ChaCha20-Poly1305): batch work takes its CUs back between
+ * _yield and _note_batch; _run serves one record of the single-record engine (> 0: not taken) */
+int tlsrec__server_yield(void);
+void tlsrec__server_note_batch(hipStream_t stream, int counted);
+int tlsrec__server_run(int dec, uint32_t cipher, uint32_t nr, const tlsrec_batch_rec *rec, const void *slot_state,
+                       const void *ghtab, const void *hpw, unsigned char *buf, size_t buf_len, const void *plan,
+                       int skip, tlsrec_batch_res *out);
 hipError_t tlsrec__launch_bucket_zero(const tlsrec::BucketArgs *a, hipStream_t st);
 hipError_t tlsrec__launch_bucket_count(const tlsrec::BucketArgs *a, hipStream_t st);
 hipError_t tlsrec__launch_bucket_scatter(const tlsrec::BucketArgs *a, hipStream_t st);
@@ -260,10 +322,10 @@ hipError_t tlsrec__exclusive_scan(const uint32_t *in, uint32_t *out, uint32_t n,
 hipError_t tlsrec__launch_res_guard(tlsrec_batch_res *res, uint32_t n, hipStream_t st);
 }
 
-/* Launch log (test hooks): the host-side dispatchers of engine.hip and
+/* Launch log (test hooks): the host-side dispatchers of batch.hip and
  * stream.hip note which kernel shape they chose, one fixed-size entry
  * {kind, p0, p1, p2, p3} per dispatch, so a test can assert the path its
- * shape was built for (tlsrec__test_launch_log_reset / _read, engine.hip).
+ * shape was built for (tlsrec__test_launch_log_reset / _read, batch.hip).
  * In the release library the macro expands to nothing.
  *   GCM             p0 lanes per record, p1 waves code (-32 paired wave passes,
  *                   -8 wave passes, -16 the CID variant, else waves per
@@ -296,9 +358,6 @@ enum {
     TLSREC_LOG_CBC = 9,
     TLSREC_LOG_CBC_KERNEL = 10
 };
-/* not exported from the library: shared between its units only */
-#define TLSREC_LOCAL __attribute__((visibility("hidden")))
-
 /* keysched.hip: the single-shot calls' device arena (32 KiB) and its stream, for a unit that stages a batch of one
  * there (cookie.hip).  tlsrec_ks_arena_lock creates both on first use; on 0 the caller holds the arena's lock until
  * tlsrec_ks_arena_unlock, on an error it holds nothing. */

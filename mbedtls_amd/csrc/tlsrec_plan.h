@@ -4,7 +4,7 @@
  * gcm_plan() and chacha_plan() decide, from a batch's record count, the key
  * table, the caller's hints and the TLSREC_GCM_* switches, which kernel family
  * runs and with what lanes per record, records per wave and grid.  Plain
- * C++17 without a HIP include: engine.hip launches what they return, a host
+ * C++17 without a HIP include: batch.hip launches what they return, a host
  * compiler can build and sweep them alone (tests/c/plan_sweep.cpp), and
  * tests/test_gcm_plan_cpu.py holds them to tests/golden/gcm_plan.json, the
  * shapes recorded on the device before the rule moved here.

@@ -6,7 +6,7 @@ both calls are send_impl<W> over one set of kernels: record edges and odd
 input offsets, few connections of many records, and every launch shape the
 engine picks with src_off set.  Each test asserts its path from the
 dispatchers' launch log; shapes are sized from the device's CU count by the
-rules of engine.hip batch()."""
+rules of batch.hip batch()."""
 import pytest
 
 pytestmark = pytest.mark.gpu

@@ -19,7 +19,7 @@ for u in $UNITS; do
 done
 for p in "${pids[@]}"; do wait "$p"; done
 objs=()
-for u in gcm_dec gcm_enc gcm_alt_dec gcm_alt_enc kernels engine keysched tls13_ladder tls12_batch exporter cookie stream ccm cbc cbc_alt cbc_wave ticket transcript x25519 server tlsrec_host; do
+for u in gcm_dec gcm_enc gcm_alt_dec gcm_alt_enc kernels keytab scratch batch host_pipe engine keysched tls13_ladder tls12_batch exporter cookie stream ccm cbc cbc_alt cbc_wave ticket transcript x25519 server tlsrec_host; do
   if [ -f "$O/$u.o" ] && [[ " $UNITS " == *" $u "* ]]; then objs+=("$O/$u.o"); else objs+=("$R/build/$u.o"); fi
 done
 "$HIPCC" -shared -fPIC --offload-arch=gfx950 -o "$R/ablib/$name.so" "${objs[@]}"
